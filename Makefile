@@ -16,7 +16,7 @@ smoke:
 	$(PY) -c "import __graft_entry__ as g; g.build(); g.smoke()"
 
 bench:            ## env steps/s + roofline + cpu_baseline JSON line
-	$(PY) bench.py
+	$(PY) bench.py --full
 
 golden:           ## regenerate tests/golden from the reference checkout (build container only)
 	$(PY) tests/golden/make_golden.py

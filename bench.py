@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — env steps/sec of the batched active-vision observation path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
 
 A "step" is one pass of the hot path over one batch of synthetic input that is
 already resident in HBM: K1 ingest (2 raw RGB frames per env -> gray -> OpenCV
@@ -9,6 +9,13 @@ fixed-point resize -> 2-frame max -> frame-stack ring) followed by the fovea
 kernel (sensory action -> crop -> bilinear resize to 84x84, f32 out).
 Workload = BASELINE.json configs[1]: 1024x AtariFixedFovealEnv per GPU, 84x84 obs,
 30x30 fovea, frame_stack=4, action_repeat=4 (=> two sampled frames per step).
+
+A plain run does only what the headline needs: set up, pre-roll / rehearse / warm
+up, time exactly K steps, write the outputs of the last timed step if
+--dump-outputs is given, print the line.  --full adds everything else measured
+after the timed region: the per-kernel HIP-event sampling pass behind `roofline` /
+`kernels`, the obs-pool and compact-input passes, the PCIe-inclusive `e2e` leg and
+the `cpu_baseline` (each can still be dropped with its --no-* option).
 
 For N>1 the driver launches one rank per GPU via torch.distributed.run; envs shard
 by contiguous index blocks, there is no data-path collective (weak scaling).
@@ -26,24 +33,32 @@ for _p in (REPO, os.path.join(REPO, "active-gym_amd")):
     if _p not in sys.path:
         sys.path.insert(0, _p)
 
-HBM_PEAK_GBS = 8000.0      # MI355X HBM3E spec peak (/opt/skills/guides/MI355X_MICROARCH.md)
+HBM_PEAK_GBS = 8000.0      # MI355X HBM3E spec peak (MI355X_MICROARCH.md)
+DUMP_BUDGET = 60_000_000   # bytes of array data --dump-outputs writes at most (64 MB in all with the .npy headers and row indices)
+REHEARSAL_CAP = 1000       # steps per rehearsal at most: the rehearsals warm up the first synchronize cycle, not the steps
 
 
-def parse():
+def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=300)
+    ap.add_argument("--steps", type=int, default=300, help="timed steps")
     ap.add_argument("--warmup", type=int, default=30)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region, also run the sampling pass (roofline, kernels), the obs-pool and compact-input "
+                         "passes, the e2e leg and the CPU baseline; a plain run only times the steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (observations, fov_loc, ...) as DIR/<name>.npy, float32 / float64, "
+                         "a fixed seeded sample of envs where the whole would exceed 60 MB (rank 0 only)")
     ap.add_argument("--envs", type=int, default=1024, help="envs per GPU")
     ap.add_argument("--kind", default="fixed", choices=["fixed", "peripheral", "flexible"])
     ap.add_argument("--pool", type=int, default=8, help="distinct synthetic input batches cycled through")
-    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="budget of the CPU-baseline sample")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-e2e", action="store_true", help="skip the PCIe-inclusive AtariVecEnv leg (the `e2e` key)")
+    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="budget of the CPU-baseline sample (--full)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-e2e", action="store_true", help="--full without the PCIe-inclusive AtariVecEnv leg (the `e2e` key)")
     ap.add_argument("--frame-format", default="rgb", choices=("rgb", "gray"),
                     help="rgb = the metric's workload (raw RGB screens, luminance on the device); gray = ALE grayscale "
                          "screens in (agx_ingest_gray_raw) - a different, lighter workload, reported for DESIGN.md only")
-    ap.add_argument("--no-events", action="store_true", help="skip the per-kernel HIP-event sampling pass (no `roofline`)")
+    ap.add_argument("--no-events", action="store_true", help="--full without the per-kernel HIP-event sampling pass (no `roofline`)")
     ap.add_argument("--antialias", type=int, default=1, choices=(0, 1),
                     help="peripheral / flexible kinds: torchvision Resize's antialias setting (SURVEY.md 8d: both are sub-runs)")
     ap.add_argument("--out", default="full", choices=("full", "packed"),
@@ -56,20 +71,20 @@ def parse():
                     help="untimed steps run BEFORE the warmup so that a short run (the driver's --steps 20) is not timed on the "
                          "first milliseconds of an idle device (clock ramp); not part of `warmup` or `steps`")
     ap.add_argument("--rehearsals", type=int, default=4,
-                    help="untimed dress rehearsals of the timed region (synchronize, `steps` steps, synchronize) between the pre-roll and "
-                         "the warmup: the first synchronize -> launch -> synchronize cycle of a process runs 1-2.5 us per step slower "
-                         "than the following ones (profiles/r04_region_sequence.txt)")
+                    help="untimed dress rehearsals of the timed region (synchronize, `steps` steps but at most %d, synchronize) between "
+                         "the pre-roll and the warmup: the first synchronize -> launch -> synchronize cycle of a process runs 1-2.5 us "
+                         "per step slower than the following ones (profiles/r04_region_sequence.txt)" % REHEARSAL_CAP)
     ap.add_argument("--samples", type=int, default=24,
-                    help="launch pairs carrying their own HIP events in the sampling pass that FOLLOWS the timed region")
+                    help="--full: launch pairs carrying their own HIP events in the sampling pass that FOLLOWS the timed region")
     ap.add_argument("--obs-pool", type=int, default=3,
-                    help="second sampling pass of the fovea kernel with its output rotating through this many observation "
+                    help="--full: second sampling pass of the fovea kernel with its output rotating through this many observation "
                          "buffers (3 x 115.6 MB no longer fits the 256 MB Infinity Cache: `kernels_obs_pool` is the kernel "
                          "against HBM, `kernels` the product's double-buffered form); 0 = skip")
     ap.add_argument("--host-wait", default="spin", choices=("spin", "yield", "auto"),
                     help="how the host thread waits in synchronize() at the end of the timed region (hipSetDeviceFlags)")
     ap.add_argument("--compact", action="store_true",
                     help="time the step on COMPACT input screens (only the 168 of 210 rows K1 reads, agx_ingest_compact: what the "
-                         "host runner stages) instead of whole screens; the default run reports it beside `value` as `compact_input`")
+                         "host runner stages) instead of whole screens; a --full run reports it beside `value` as `compact_input`")
     ap.add_argument("--event-mode", default="kernel", choices=("kernel", "stream"),
                     help="kernel: start/stop HIP events stamped by the launch itself (hipExtLaunchKernelGGL through "
                          "agx_profile_next: the kernel's own begin/end, what rocprofv3 reports); stream: events recorded "
@@ -77,7 +92,7 @@ def parse():
     ap.add_argument("--event-every", type=int, default=4,
                     help="sampling pass: every M-th step carries the events, the steps between run plain so that a sampled "
                          "launch sees the same neighbours as in the timed region")
-    return ap.parse_args()
+    return ap.parse_args(argv)
 
 
 def synth_inputs(torch, dev, n, pool, seed, gray=False):
@@ -130,6 +145,47 @@ def make_pipeline(kind, n, dev, antialias=True, packed=False):
     if packed:          # ragged raw crops (fov_env.py:283-298): neither mask_out nor resize_to_full
         return ObsPipeline(kind="flexible", resize_to_full=False, mask_out=False, antialias=antialias, **kw)
     return ObsPipeline(kind="flexible", resize_to_full=True, antialias=antialias, **kw)
+
+
+def _dump_dtype(dtype):
+    """float32 / float64 outputs keep their type; integers (fov_loc, offsets) go to float64, which holds them exactly."""
+    name = str(dtype).replace("torch.", "")
+    return name if name in ("float32", "float64") else "float64"
+
+
+def dump_selection(sizes, budget=DUMP_BUDGET, seed=0):
+    """sizes: {name: (rows, bytes per row at the dumped type)}.  Returns {name: None (every row) | sorted row indices}: all
+    outputs whole when they fit `budget`; otherwise those of at most 1 MB stay whole and the larger ones are cut to the same
+    share of their rows (axis 0, envs), a fixed sample drawn from a seeded generator, so that runs with the same arguments
+    write the same rows."""
+    import numpy as np
+    total = sum(r * b for r, b in sizes.values())
+    if total <= budget:
+        return {k: None for k in sizes}
+    small = {k for k, (r, b) in sizes.items() if r * b <= 1 << 20}
+    left = budget - sum(sizes[k][0] * sizes[k][1] for k in small)
+    big = {k: v for k, v in sizes.items() if k not in small}
+    frac = left / sum(r * (b + 8) for r, b in big.values())      # + 8: the float64 row index written beside each sample
+    sel = {k: None for k in small}
+    for k, (r, b) in big.items():
+        m = max(1, int(r * frac))
+        sel[k] = np.sort(np.random.default_rng(seed).choice(r, m, replace=False))
+    return sel
+
+
+def dump_outputs(out_dir, outputs, budget=DUMP_BUDGET, seed=0):
+    """Write {name: tensor} as out_dir/<name>.npy (see _dump_dtype); a sampled output also gets out_dir/<name>_rows.npy, the
+    row indices it holds (float64).  Rows are selected on the device, so only the sample crosses PCIe."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    sizes = {k: (int(t.shape[0]), int(t[:1].numel()) * np.dtype(_dump_dtype(t.dtype)).itemsize) for k, t in outputs.items()}
+    sel = dump_selection(sizes, budget, seed)
+    for k, t in outputs.items():
+        if sel[k] is not None:
+            t = t.index_select(0, torch.from_numpy(sel[k]).to(t.device))
+            np.save(os.path.join(out_dir, k + "_rows.npy"), sel[k].astype(np.float64))
+        np.save(os.path.join(out_dir, k + ".npy"), t.cpu().numpy().astype(_dump_dtype(t.dtype), copy=False))
 
 
 _CPU_CHILD = r"""
@@ -554,7 +610,7 @@ def main():
     K = args.steps
     for _ in range(max(0, args.rehearsals)):
         torch.cuda.synchronize(dev)
-        for k in range(K):
+        for k in range(min(K, REHEARSAL_CAP)):
             step(k)
         torch.cuda.synchronize(dev)
     for k in range(args.warmup):
@@ -572,10 +628,19 @@ def main():
     barrier(dist, local_rank)
     per_rank = all_ranks(elapsed, dist, dev)                 # every rank's own duration of the timed region
     elapsed = max_over_ranks(elapsed, dist, dev)
+    if args.dump_outputs and rank == 0:
+        # what the last timed step handed its caller, before anything below steps the pipeline again
+        if packed_mode:
+            outputs = {"packed": packed_buf[:int(offsets[-1].item())], "offsets": offsets, "fov_loc": loc, "fov_res": res_out}
+        else:
+            outputs = {"obs": obs, "fov_loc": loc}
+            if args.kind == "flexible":
+                outputs["fov_res"] = res_out
+        dump_outputs(args.dump_outputs, outputs)
 
     # the sampling pass (untimed, rank 0 only; the ranks share nothing): the same step loop continues, and every M-th step's two
     # launches carry their own start / stop events, on the launch stream (torch's current stream is the one handed to the C ABI)
-    use_ev = not args.no_events and rank == 0
+    use_ev = args.full and not args.no_events and rank == 0
     M = max(1, args.event_every)
     S = max(16, args.samples)
 
@@ -631,15 +696,16 @@ def main():
 
     # the PCIe- and emulator-inclusive leg runs on EVERY rank at the same time (eight ranks share one host's cores, memory
     # system and PCIe root complexes: that is what it is there to show); rank 0 prints them all
+    use_e2e = args.full and not args.no_e2e
     e2e_mine = None
-    if not args.no_e2e:
+    if use_e2e:
         barrier(dist, local_rank)
         try:
             e2e_mine = run_e2e(dev, n, host_cores(), rank)
         except Exception as ex:  # noqa: BLE001 - a reported extra, never the metric
             e2e_mine = {"error": repr(ex)}
     e2e_all = [e2e_mine]
-    if dist is not None and dist.is_initialized() and world > 1 and not args.no_e2e:
+    if dist is not None and dist.is_initialized() and world > 1 and use_e2e:
         e2e_all = [None] * world
         dist.all_gather_object(e2e_all, e2e_mine)
 
@@ -686,6 +752,7 @@ def main():
             "metric": "env steps/sec at N=1024 AtariFixedFovealEnv; 1/2/4/8-GPU scaling",
             "value": total_envs * K / elapsed, "unit": "env steps/s", "n_gpus": world, "steps": K, "warmup": args.warmup,
             "preroll": args.preroll, "rehearsals": args.rehearsals, "events_in_timed_region": events_in_timed_region, "host_wait": host_wait,
+            "full": bool(args.full),
             "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
             "dtype": "u8 ingest / f32 resize", "data": "synthetic",
             "config": {"workload": workload_name(args, n, packed_mode, gray, use_compact),
@@ -720,7 +787,7 @@ def main():
                         "reads, agx_ingest_compact): same results, same algorithmic bytes; never `value`" % int(src_rows.numel())}
         if world > 1:
             out["config"]["games"] = "one synthetic frame source per GPU (the game mix only changes the emulator, never the shapes)"
-        if not args.no_e2e:
+        if use_e2e:
             if world == 1:
                 out["e2e"] = e2e_all[0]
             else:
@@ -732,7 +799,7 @@ def main():
                     out["e2e_aggregate"]["ranks"] = len(ok)
                 except (KeyError, TypeError) as ex:      # a rank's leg came back incomplete: the line still goes out
                     out["e2e_aggregate"] = {"error": repr(ex), "ranks": len(ok)}
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(args.cpu_seconds, 1234)
         print(json.dumps(out), flush=True)
     if dist is not None:

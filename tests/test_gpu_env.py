@@ -428,10 +428,10 @@ def test_reset_does_not_overwrite_the_observation_the_caller_holds(kind):
 
 
 def test_bench_contract_json():
-    """bench.py prints ONE JSON line with the driver's contract fields (small, quick configuration)."""
+    """bench.py --full prints ONE JSON line with the driver's contract fields (small, quick configuration)."""
     import json, os, subprocess, sys
     repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    out = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--steps", "8", "--warmup", "2", "--envs", "64",
+    out = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--full", "--steps", "8", "--warmup", "2", "--envs", "64",
                           "--cpu-seconds", "3"], capture_output=True, text=True, timeout=600, cwd=repo)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -460,6 +460,44 @@ def test_bench_contract_json():
     assert "error" not in e, e
     assert e["rgb"]["rows_staged_per_screen"] == 168 and e["rgb"]["h2d_bytes_per_step"] == 64 * 2 * 168 * 160 * 3
     assert e["placement"]["workers"] >= 1 and e["step_loop"].startswith("native")
+
+
+def test_bench_plain_run_dumps_the_last_timed_step(tmp_path):
+    """A plain bench.py run times the steps and nothing else, and --dump-outputs writes what the last timed step computed:
+    float32 / float64 .npy files, the same bytes from run to run with the same arguments."""
+    import json, os, subprocess, sys
+    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+    def run(tag, *extra):
+        d = tmp_path / tag
+        r = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--steps", "8", "--warmup", "2", "--envs", "64",
+                            "--dump-outputs", str(d), *extra], capture_output=True, text=True, timeout=600, cwd=repo)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1
+        return json.loads(lines[0]), {f[:-4]: np.load(d / f) for f in sorted(os.listdir(d))}
+
+    d, a = run("a")
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in d, k
+    assert d["steps"] == 8 and d["full"] is False and d["events_in_timed_region"] == 0
+    assert abs(d["value"] - 64 * 8 / (d["ms_per_step"] * 8e-3)) / d["value"] < 1e-6
+    assert d["roofline"] is None and d["kernels"] == {}
+    for k in ("cpu_baseline", "e2e", "compact_input", "kernels_obs_pool"):
+        assert k not in d, k
+    assert sorted(a) == ["fov_loc", "obs"]                                # 64 envs fit the budget whole: no sampled rows
+    assert a["obs"].dtype == np.float32 and a["obs"].shape == (64, 4, 84, 84)
+    assert a["fov_loc"].dtype == np.float64 and a["fov_loc"].shape == (64, 2)
+    assert a["obs"].min() >= 0 and a["obs"].max() <= 1 and a["obs"].std() > 0
+    assert np.array_equal(a["fov_loc"], np.rint(a["fov_loc"])) and a["fov_loc"].min() >= 0 and a["fov_loc"].max() <= 84 - 30
+    _, b = run("b")
+    assert sorted(b) == sorted(a) and all(np.array_equal(a[k], b[k]) for k in a)
+    # the ragged raw-crop sub-run hands out packed crops + offsets: env n's crops are packed[offsets[n]:offsets[n+1]] = [fs, rh, rw]
+    _, p = run("packed", "--kind", "flexible", "--out", "packed")
+    assert sorted(p) == ["fov_loc", "fov_res", "offsets", "packed"]
+    assert p["packed"].dtype == np.float32 and p["offsets"].dtype == np.float64 and p["offsets"][0] == 0
+    assert p["packed"].shape == (int(p["offsets"][-1]),)
+    assert np.array_equal(np.diff(p["offsets"]), 4 * p["fov_res"][:, 0] * p["fov_res"][:, 1])
 
 
 @pytest.mark.parametrize("kind", ["fixed", "flex", "per"])

@@ -83,7 +83,7 @@ def test_two_ranks_on_the_device_path_reproduce_the_unsharded_run(chunk):
 def test_bench_two_gpu_rehearsal_prints_one_line_with_per_gpu_values():
     env = dict(os.environ, AGX_BENCH_SHARE_GPU="1", AGX_BENCH_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
     r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--steps", "24", "--warmup", "4", "--envs", "256",
-                        "--no-cpu-baseline"], capture_output=True, text=True, cwd=REPO, env=env, timeout=900)
+                        "--full", "--no-cpu-baseline"], capture_output=True, text=True, cwd=REPO, env=env, timeout=900)
     assert r.returncode == 0, r.stdout + r.stderr
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, r.stdout

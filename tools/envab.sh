@@ -1,7 +1,7 @@
 #!/bin/bash
 # usage: tools/envab.sh "VAR=1" ["VAR2=3" ...] ; bench.py (300 steps, kernel events) with each environment setting, default first and last
 set -u
-B="python3 bench.py --steps 300 --warmup 20 --no-cpu-baseline --no-e2e"
+B="python3 bench.py --full --steps 300 --warmup 20 --no-cpu-baseline --no-e2e"
 sum() { python3 -c "
 import json,sys
 d=json.loads(open(sys.argv[1]).read().strip().split('\n')[-1])

@@ -15,18 +15,18 @@ python3 -c "import sys; sys.path.insert(0, 'active-gym_amd'); from active_gym im
 SUB="peripheral:--kind@peripheral@--antialias@1 peripheral_aa0:--kind@peripheral@--antialias@0 flexible:--kind@flexible@--antialias@1 flexible_aa0:--kind@flexible@--antialias@0 flexible_packed:--kind@flexible@--out@packed flexible_packed_aa0:--kind@flexible@--out@packed@--antialias@0"
 if [ "$PART" = all ] || [ "$PART" = 1 ]; then
   echo "== bench lines"
-  python3 bench.py > $OUT/bench.json 2> $OUT/bench.err
-  python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-e2e > $OUT/bench_driver_form.json 2>> $OUT/bench.err
+  python3 bench.py --full > $OUT/bench.json 2> $OUT/bench.err
+  python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-e2e > $OUT/bench_driver_form.json 2>> $OUT/bench.err
   for s in $SUB; do
     name=${s%%:*}; args=$(echo ${s#*:} | tr '@' ' ')
-    python3 bench.py $args --no-cpu-baseline --no-e2e > $OUT/bench_$name.json 2>> $OUT/bench.err
+    python3 bench.py --full $args --no-cpu-baseline --no-e2e > $OUT/bench_$name.json 2>> $OUT/bench.err
   done
-  python3 bench.py --frame-format gray --no-cpu-baseline --no-e2e > $OUT/bench_gray_frames.json 2>> $OUT/bench.err
+  python3 bench.py --full --frame-format gray --no-cpu-baseline --no-e2e > $OUT/bench_gray_frames.json 2>> $OUT/bench.err
   echo "== kernel trace"
   for s in fixed: $SUB; do
     name=${s%%:*}; args=$(echo ${s#*:} | tr '@' ' ')
     # --obs-pool 0: the trace's average of the fovea kernel is then the product form alone (the pool pass has its own events)
-    timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kt_$name -- python3 bench.py $args --obs-pool 0 --no-cpu-baseline --no-e2e > $OUT/bench_under_rocprof_$name.json 2> $OUT/kt_$name.err || echo "kernel trace $name failed"
+    timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kt_$name -- python3 bench.py --full $args --obs-pool 0 --no-cpu-baseline --no-e2e > $OUT/bench_under_rocprof_$name.json 2> $OUT/kt_$name.err || echo "kernel trace $name failed"
     f=$(find $OUT/kt_$name -name '*kernel_stats.csv' | head -1)
     [ -n "$f" ] && { head -1 $f; grep 'agx::' $f; } > $OUT/kernel_stats_$name.csv
   done
