@@ -13,6 +13,7 @@ ABI_VERSION = 2
 OK, E_INVALID, E_HIP, E_NOMEM, E_STATE = 0, -1, -2, -3, -4
 KIND_BASE, KIND_FIXED, KIND_FLEXIBLE, KIND_PERIPHERAL = 0, 1, 2, 3
 OUT_RAW, OUT_RESIZE, OUT_MASK = 0, 1, 2
+OBS_F32, OBS_BF16, OBS_F16, OBS_TYPE_MASK = 0x00, 0x10, 0x20, 0x30     # element type bits of out_mode
 MODE_ABSOLUTE, MODE_RELATIVE = 0, 1
 DT_F32, DT_F64, DT_I32, DT_I64 = 0, 1, 2, 3
 FOV_LOC, FOV_RES = 0, 1

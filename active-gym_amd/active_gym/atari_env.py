@@ -18,7 +18,8 @@ class AtariEnvArgs:
     ``fov_size, fov_init_loc, sensory_action_mode, resize_to_full`` (+ ``sensory_action_space`` for
     relative mode, ``peripheral_res`` for the peripheral env) have no defaults there either.
     Additional optional attributes understood here: ``frame_source``, ``antialias``, ``num_workers``;
-    ``device`` (None in the reference and unused) selects NumPy (None) or device-tensor outputs."""
+    ``device`` (None in the reference and unused) selects NumPy (None) or device-tensor outputs; ``obs_dtype``
+    ("float32" by default, "bfloat16" - device outputs only - or "float16", or the torch dtype) the observation element type."""
 
     def __init__(self, game, seed, obs_size: Tuple[int, int], **kwargs):
         self.env_backend = "atari_py"
@@ -32,6 +33,7 @@ class AtariEnvArgs:
         self.mask_out = False
         self.record = False
         self.clip_reward = False
+        self.obs_dtype = "float32"
         for k, v in kwargs.items():
             self.__setattr__(k, v)
 
@@ -79,7 +81,9 @@ class AtariEnv(_SingleEnv):
         self.actions = dict(enumerate(self._core.runner.actions[0]))
         from .spaces import Box, Discrete
         self.action_space = Discrete(len(self.actions))
-        self.observation_space = Box(low=-1., high=1., shape=(self.frame_stack,) + self.obs_size, dtype=np.float32)
+        self.obs_dtype = self._core.obs_dtype
+        self.observation_space = Box(low=-1., high=1., shape=(self.frame_stack,) + self.obs_size,
+                                     dtype=self._core.single_observation_space.dtype)
 
     def _rekind(self, kind):
         """A fovea wrapper switches the core to its own kernel kind (before the first reset); the emulator is kept."""

@@ -44,6 +44,7 @@ class DMCEnvArgs:
         self.clip_reward = False
         self.record = False
         self.device = None
+        self.obs_dtype = "float32"           # observation element type, as AtariEnvArgs.obs_dtype
         for k, v in kwargs.items():
             self.__setattr__(k, v)
 
@@ -252,7 +253,9 @@ class DMCEnv(_SingleEnv):
         r = self._core.runner
         self._true_action_space = Box(r.true_low, r.true_high, dtype=np.float32)
         self._norm_action_space = self._core.single_motor_space
-        self._observation_space = Box(low=-1., high=1., shape=(self.frame_stack,) + self.obs_size, dtype=np.float32)
+        self.obs_dtype = self._core.obs_dtype
+        self._observation_space = Box(low=-1., high=1., shape=(self.frame_stack,) + self.obs_size,
+                                      dtype=self._core.single_observation_space.dtype)
         lo, hi = _bounds(r.envs[0].observation_spec().values(), np.float32)
         self._state_space = Box(lo, hi, dtype=np.float32)
 

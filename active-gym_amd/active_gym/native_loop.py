@@ -169,7 +169,11 @@ class NativeStepLoop:
         idx = self._host("done_idx", r.done_idx, np.int32)[:k].copy() if k else np.zeros(0, np.int32)
         fo = fl = fr = None
         if k and r.d_final_obs:
-            fo = self._device("final_obs", r.d_final_obs, (n,) + tuple(obs.shape[1:]), "<f4")[:k]
+            # the terminal rows are elements of the observation's type (bfloat16 has no array-interface type string: int16 bits)
+            ts = {torch.float32: "<f4", torch.float16: "<f2", torch.bfloat16: "<i2"}[obs.dtype]
+            fo = self._device("final_obs", r.d_final_obs, (n,) + tuple(obs.shape[1:]), ts)[:k]
+            if obs.dtype is torch.bfloat16:
+                fo = fo.view(torch.bfloat16)
             if r.d_final_loc:
                 fl = self._device("final_loc", r.d_final_loc, (n, 2), "<i4")[:k]
             if r.d_final_res:

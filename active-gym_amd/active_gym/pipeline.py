@@ -21,6 +21,23 @@ from . import _native as nat
 _KINDS = {"base": nat.KIND_BASE, "fixed": nat.KIND_FIXED, "flexible": nat.KIND_FLEXIBLE,
           "peripheral": nat.KIND_PERIPHERAL}
 _DT = {torch.float32: nat.DT_F32, torch.float64: nat.DT_F64, torch.int32: nat.DT_I32, torch.int64: nat.DT_I64}
+# observation element types: name -> (torch dtype, agx_config.out_mode bits)
+OBS_DTYPES = {"float32": (torch.float32, nat.OBS_F32), "bfloat16": (torch.bfloat16, nat.OBS_BF16),
+              "float16": (torch.float16, nat.OBS_F16)}
+
+
+def resolve_obs_dtype(obs_dtype) -> torch.dtype:
+    """``"float32" | "bfloat16" | "float16"`` or the torch dtype itself -> the torch dtype; ValueError for anything else."""
+    for name, (dt, _) in OBS_DTYPES.items():
+        if obs_dtype is dt or (isinstance(obs_dtype, str) and obs_dtype == name):
+            return dt
+    raise ValueError(f"obs_dtype must be one of {sorted(OBS_DTYPES)} (or the torch dtype), got {obs_dtype!r}")
+
+
+def obs_dtype_bits(obs_dtype) -> int:
+    """The AGX_OBS_* bits of an observation element type."""
+    dt = resolve_obs_dtype(obs_dtype)
+    return next(bits for t, bits in OBS_DTYPES.values() if t is dt)
 
 
 def resolve_out_mode(mask_out: bool, resize_to_full: bool) -> int:
@@ -38,7 +55,10 @@ class ObsPipeline:
                  fov_init_loc: Sequence[float] = (0, 0), sensory_action_mode: str = "absolute",
                  sensory_action_space: Optional[Sequence[float]] = None, resize_to_full: bool = False,
                  mask_out: bool = False, peripheral_res: Optional[Tuple[int, int]] = None,
-                 antialias: bool = True, device: Optional[torch.device] = None):
+                 antialias: bool = True, device: Optional[torch.device] = None, obs_dtype=torch.float32):
+        """obs_dtype: element type of every observation this pipeline writes - float32 (default), bfloat16 or float16 (a torch
+        dtype or its name).  The values are the float32 ones rounded to nearest-even once (include/agx.h, AGX_OBS_*)."""
+        self.obs_dtype = resolve_obs_dtype(obs_dtype)
         if not torch.cuda.is_available():
             raise RuntimeError("ObsPipeline needs a ROCm GPU: the observation path has no CPU implementation")
         self._lib = nat.lib()
@@ -87,6 +107,7 @@ class ObsPipeline:
             cfg.antialias = 1 if antialias else 0
         self.fov_size = (cfg.fov_h, cfg.fov_w)
         self.out_mode = cfg.out_mode
+        cfg.out_mode |= obs_dtype_bits(self.obs_dtype)
         self._cfg = cfg
         self._ctx = C.c_void_p()
         nat.check(self._lib.agx_create(C.byref(cfg), C.byref(self._ctx)))
@@ -203,8 +224,8 @@ class ObsPipeline:
             pa = self._chk(action, (N, 2), None, "action")
             dt = _DT[action.dtype]
         if out is None:
-            out = torch.empty(self.obs_shape, dtype=torch.float32, device=self.device)
-        po = self._chk(out, self.obs_shape, torch.float32, "out")
+            out = torch.empty(self.obs_shape, dtype=self.obs_dtype, device=self.device)
+        po = self._chk(out, self.obs_shape, self.obs_dtype, "out")
         if loc_out is None:
             loc_out = torch.empty((N, 2), dtype=torch.int32, device=self.device)
         pl = self._chk(loc_out, (N, 2), torch.int32, "loc_out")
@@ -222,8 +243,8 @@ class ObsPipeline:
 
     def observe_full(self, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         if out is None:
-            out = torch.empty(self.full_shape, dtype=torch.float32, device=self.device)
-        po = self._chk(out, self.full_shape, torch.float32, "out")
+            out = torch.empty(self.full_shape, dtype=self.obs_dtype, device=self.device)
+        po = self._chk(out, self.full_shape, self.obs_dtype, "out")
         nat.check(self._lib.agx_observe_full(self._ctx, po, self._stream()), self._ctx)
         return out
 
@@ -349,8 +370,8 @@ class ObsPipeline:
             dt = _DT[action.dtype]
         pm = self._chk(mask, (N,), torch.uint8, "mask") if mask is not None else None
         if out is None:
-            out = torch.empty(self.obs_shape, dtype=torch.float32, device=self.device)
-        po = self._chk(out, self.obs_shape, torch.float32, "out")
+            out = torch.empty(self.obs_shape, dtype=self.obs_dtype, device=self.device)
+        po = self._chk(out, self.obs_shape, self.obs_dtype, "out")
         if loc_out is None:
             loc_out = torch.empty((N, 2), dtype=torch.int32, device=self.device)
         pl = self._chk(loc_out, (N, 2), torch.int32, "loc_out")

@@ -23,7 +23,7 @@ import numpy as np
 import torch
 
 from . import _native as nat
-from .pipeline import ObsPipeline
+from .pipeline import ObsPipeline, resolve_obs_dtype
 from .runner import AtariHostRunner
 from .spaces import Box, Dict, Discrete, batch_space
 
@@ -34,6 +34,27 @@ def _resolve_antialias(args):
     """torchvision's Resize default: antialias=True from 0.17 on (the reference leaves the version
     unpinned, setup.py:17).  ``args.antialias`` overrides."""
     return bool(getattr(args, "antialias", True))
+
+
+def _resolve_env_obs_dtype(args):
+    """``args.obs_dtype`` ("float32" by default, "bfloat16", "float16" or the torch dtype) -> the torch dtype, with the
+    combinations the 16-bit outputs do not serve refused up front (before any GPU work)."""
+    dt = resolve_obs_dtype(getattr(args, "obs_dtype", "float32"))
+    if dt is not torch.float32:
+        if dt is torch.bfloat16 and getattr(args, "device", None) is None:
+            raise ValueError("obs_dtype bfloat16 needs device outputs (args.device): NumPy has no bfloat16 "
+                             "(host outputs take float32 or float16)")
+        if getattr(args, "ragged_obs", "padded") == "packed":
+            raise ValueError(f"obs_dtype {dt} with ragged_obs='packed': the packed ragged crops are float32 only")
+        if bool(getattr(args, "record", False)):
+            raise ValueError(f"obs_dtype {dt} with record=True: the record buffers keep the reference's float32 format")
+    return dt
+
+
+def obs_space_dtype(obs_dtype):
+    """NumPy dtype of the observation Box: float16 for float16 outputs; float32 otherwise - bfloat16 has no NumPy dtype, its
+    Box says float32 (the values it holds are float32 values) and ``env.obs_dtype`` names the element type."""
+    return np.float16 if obs_dtype is torch.float16 else np.float32
 
 
 class _HostObsPool:
@@ -96,6 +117,7 @@ class AtariVecEnv:
         self.autoreset = bool(autoreset)        # False: single-env semantics, the caller calls reset()
         if kind not in _KINDS:
             raise ValueError(f"kind must be one of {_KINDS}")
+        self.obs_dtype = _resolve_env_obs_dtype(args)
         if not torch.cuda.is_available():
             raise RuntimeError("active_gym envs need a ROCm GPU: the observation pipeline has no CPU implementation")
         self.args = args
@@ -136,7 +158,7 @@ class AtariVecEnv:
     def _build_pipeline(self):
         args, kind = self.args, self.kind
         kw = dict(num_envs=self.num_envs, kind=kind, obs_size=self.obs_size, frame_stack=self.frame_stack,
-                  device=self.device)
+                  device=self.device, obs_dtype=self.obs_dtype)
         if kind != "base":
             # these have no defaults in the reference and are read unconditionally (fov_env.py:110-120)
             self.fov_size = tuple(int(v) for v in args.fov_size)
@@ -169,7 +191,7 @@ class AtariVecEnv:
         full = (self.frame_stack,) + self.obs_size
         if kind == "base":
             self.single_action_space = self.single_motor_space
-            self.single_observation_space = Box(low=-1., high=1., shape=full, dtype=np.float32)
+            self.single_observation_space = Box(low=-1., high=1., shape=full, dtype=obs_space_dtype(self.obs_dtype))
         else:
             sas = self.sensory_action_space
             spaces = {"motor_action": self.single_motor_space,
@@ -179,7 +201,7 @@ class AtariVecEnv:
             self.single_action_space = Dict(spaces)
             crop = kind == "fixed" and not (self.mask_out or self.resize_to_full)
             shp = (self.frame_stack,) + (self.fov_size if crop else self.obs_size)
-            self.single_observation_space = Box(low=-1., high=1., shape=shp, dtype=np.float32)
+            self.single_observation_space = Box(low=-1., high=1., shape=shp, dtype=obs_space_dtype(self.obs_dtype))
         # SyncVectorEnv conventions (gymnasium<1.0): batched spaces under action_space / observation_space
         self.action_space = batch_space(self.single_action_space, self.num_envs)
         self.observation_space = batch_space(self.single_observation_space, self.num_envs)
@@ -201,7 +223,7 @@ class AtariVecEnv:
         # dropped the array (_HostObsPool; args.host_obs_buffers = 0 restores the pageable copy per call)
         nbuf = getattr(self.args, "host_obs_buffers", 4)
         self._host_pool = _HostObsPool(int(nbuf)) if (self._numpy_out and not self._pinned_host_obs and int(nbuf or 0) > 0) else None
-        self._obs_bufs = [torch.empty(shp, dtype=torch.float32, device=self.device)
+        self._obs_bufs = [torch.empty(shp, dtype=self.obs_dtype, device=self.device)
                           for _ in range(1 if (self._numpy_out or self._copy_obs) else 2)]
         self._obs_i = 0
         self._obs = self._obs_bufs[0]

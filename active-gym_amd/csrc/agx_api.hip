@@ -22,7 +22,8 @@
 using namespace agx;
 
 struct agx_ctx {
-    agx_config cfg;
+    agx_config cfg;            // cfg.out_mode holds the mode only (AGX_OUT_*); its element type bits are obs_type
+    int obs_type = AGX_OBS_F32;   // AGX_OBS_F32 | AGX_OBS_BF16 | AGX_OBS_F16
     uint8_t *ring = nullptr;
     int32_t *head[2] = {nullptr, nullptr};
     int32_t *loc[2] = {nullptr, nullptr};
@@ -302,6 +303,18 @@ int upload_owned(agx_ctx *ctx, const T **dptr, const std::vector<T> &h) {
 
 bool has_fovea(const agx_config &c) { return c.kind != AGX_KIND_BASE; }
 
+// Calls f(OT{}) with the observation element type of AGX_OBS_* `t` (float, __bf16, _Float16): every launch of a kernel that
+// writes observations goes through this, the f32 instantiations are the kernels as they were before the 16-bit outputs.
+template <class F>
+int with_obs_type(int t, F &&f) {
+    switch (t) {
+        case AGX_OBS_BF16: return f(__bf16{});
+        case AGX_OBS_F16: return f(_Float16{});
+        default: return f(float{});
+    }
+}
+int obs_elem_bytes(int t) { return t == AGX_OBS_F32 ? 4 : 2; }
+
 size_t fixed_lds(const agx_config &c) {
     // window rows u8 [fh][ow] (16-B padded) | ytab[oh] | H[fh][ow]   (the carve of fovea_fixed_body)
     const size_t raw = ((size_t)c.fov_h * c.obs_w + 15) & ~(size_t)15;
@@ -397,7 +410,13 @@ int agx_create(const agx_config *cfg, agx_ctx **out) {
     if (cfg->struct_size != (int32_t)sizeof(agx_config))
         return fail(nullptr, AGX_E_INVALID, "agx_create: struct_size %d != %zu (ABI mismatch)", cfg->struct_size,
                     sizeof(agx_config));
-    const agx_config &c = *cfg;
+    // out_mode = AGX_OUT_* | AGX_OBS_*: the context keeps the mode in cfg.out_mode and the element type in obs_type
+    const int obs_type = cfg->out_mode & AGX_OBS_TYPE_MASK;
+    if (obs_type == AGX_OBS_TYPE_MASK)
+        return fail(nullptr, AGX_E_INVALID, "out_mode 0x%x: AGX_OBS_BF16 and AGX_OBS_F16 are exclusive", cfg->out_mode);
+    agx_config c_split = *cfg;
+    c_split.out_mode = cfg->out_mode & ~AGX_OBS_TYPE_MASK;
+    const agx_config &c = c_split;
     if (c.num_envs < 1 || c.num_envs > 65535)   // env index rides on gridDim.y / gridDim.z
         return fail(nullptr, AGX_E_INVALID, "num_envs must be in [1, 65535] per context (shard larger batches)");
     if (c.raw_h != kRawH || c.raw_w != kRawW)
@@ -411,7 +430,8 @@ int agx_create(const agx_config *cfg, agx_ctx **out) {
         if (c.fov_h < 1 || c.fov_w < 1 || c.fov_h >= c.obs_h || c.fov_w >= c.obs_w)
             return fail(nullptr, AGX_E_INVALID, "fov_size (%d,%d) must be >= 1 and < obs_size (%d,%d)", c.fov_h, c.fov_w,
                         c.obs_h, c.obs_w);
-        if (c.out_mode < AGX_OUT_RAW || c.out_mode > AGX_OUT_MASK) return fail(nullptr, AGX_E_INVALID, "bad out_mode");
+        if (c.out_mode < AGX_OUT_RAW || c.out_mode > AGX_OUT_MASK)
+            return fail(nullptr, AGX_E_INVALID, "bad out_mode 0x%x (AGX_OUT_* | AGX_OBS_*)", cfg->out_mode);
         if (c.action_mode != AGX_MODE_ABSOLUTE && c.action_mode != AGX_MODE_RELATIVE)
             return fail(nullptr, AGX_E_INVALID, "bad action_mode");
         if (c.action_mode == AGX_MODE_RELATIVE && !(c.sas_lo <= c.sas_hi))
@@ -436,6 +456,7 @@ int agx_create(const agx_config *cfg, agx_ctx **out) {
     agx_ctx *ctx = new (std::nothrow) agx_ctx;
     if (!ctx) return fail(nullptr, AGX_E_NOMEM, "out of host memory");
     ctx->cfg = c;
+    ctx->obs_type = obs_type;
     ctx->tune.generic = env_int("AGX_FOVEA_GENERIC");
     ctx->tune.no_full = env_int("AGX_INGEST_NO_FULL");
     ctx->tune.flex_v2 = env_int("AGX_FLEX_V2");
@@ -694,7 +715,7 @@ int agx_profile_next(agx_ctx *ctx, int kernel_id, void *start_event, void *stop_
 int64_t agx_algorithmic_bytes(const agx_ctx *ctx, int kernel_id) {
     if (!ctx) return AGX_E_INVALID;
     const agx_config &c = ctx->cfg;
-    const int64_t N = c.num_envs, fs = c.frame_stack, px = (int64_t)c.obs_h * c.obs_w;
+    const int64_t N = c.num_envs, fs = c.frame_stack, px = (int64_t)c.obs_h * c.obs_w, e = obs_elem_bytes(ctx->obs_type);
     switch (kernel_id) {
         case AGX_K_INGEST:   // two frames, only the source rows the vertical resize touches + one u8 slot
             return N * (2 * (int64_t)ctx->rows_touched * kRawRowBytes + px);
@@ -703,13 +724,13 @@ int64_t agx_algorithmic_bytes(const agx_ctx *ctx, int kernel_id) {
         case AGX_K_INGEST_RGB:   // one obs-sized RGB render in, one u8 slot out
             return N * px * 4;
         case AGX_K_FULL:
-            return N * fs * px * 5;
+            return N * fs * px * (1 + e);
         case AGX_K_FOVEA: {
             if (!has_fovea(c)) return AGX_E_STATE;
             const int64_t win = (int64_t)c.fov_h * c.fov_w;
-            if (c.kind == AGX_KIND_PERIPHERAL) return N * fs * px * 5;
-            if (c.kind == AGX_KIND_FIXED && c.out_mode == AGX_OUT_RAW) return N * fs * win * 5;
-            return N * fs * (win + px * 4);
+            if (c.kind == AGX_KIND_PERIPHERAL) return N * fs * px * (1 + e);
+            if (c.kind == AGX_KIND_FIXED && c.out_mode == AGX_OUT_RAW) return N * fs * win * (1 + e);
+            return N * fs * (win + px * e);
         }
         default:
             return AGX_E_INVALID;
@@ -941,7 +962,11 @@ static int stack_launch(agx_ctx *ctx, int which, const uint8_t *in_u8, uint8_t *
     else if (which == 1)
         hipLaunchKernelGGL(k_set_stack, grid, dim3(kThreads), 0, S(stream), p);
     else
-        hipLaunchKernelGGL(k_full, grid, dim3(kThreads), 0, S(stream), p);
+        with_obs_type(ctx->obs_type, [&](auto tag) {
+            using OT = decltype(tag);
+            hipLaunchKernelGGL(k_full<OT>, grid, dim3(kThreads), 0, S(stream), p);
+            return 0;
+        });
     AGX_HIP(ctx, hipGetLastError());
     return AGX_OK;
 }
@@ -1068,14 +1093,14 @@ int agx_fovea_fixed(agx_ctx *ctx, const void *d_action, int action_dtype, const 
 #define LAUNCH(MODE)                                                                                  \
     do {                                                                                              \
         if (headline)                                                                                 \
-            AGX_LAUNCH(1, (k_fovea_fixed<GS, MODE>), grid, block, lds, S(stream), GS{}, p);      \
+            AGX_LAUNCH(1, (k_fovea_fixed<GS, MODE, OT>), grid, block, lds, S(stream), GS{}, p);  \
         else                                                                                          \
-            AGX_LAUNCH(1, (k_fovea_fixed<GeomR, MODE>), grid, block, lds, S(stream), gr, p);     \
+            AGX_LAUNCH(1, (k_fovea_fixed<GeomR, MODE, OT>), grid, block, lds, S(stream), gr, p); \
     } while (0)
 #ifdef AGX_EXPERIMENTS
     // two physical slots per workgroup (whole launch resident at once, second frame's load hidden): measured a tie
     // with the one-slot form at N=1024 (26.3 vs 25.8 us) - the launch is store-limited
-    if (c.out_mode == AGX_OUT_RESIZE && c.frame_stack % 2 == 0 && ctx->tune.pair == 1) {
+    if (c.out_mode == AGX_OUT_RESIZE && c.frame_stack % 2 == 0 && ctx->tune.pair == 1 && ctx->obs_type == AGX_OBS_F32) {
         const dim3 grid2(c.frame_stack / 2, c.num_envs);
         if (headline)
             hipLaunchKernelGGL((k_fovea_fixed2<GS>), grid2, block, fixed2_lds(c), S(stream), GS{}, p);
@@ -1083,11 +1108,15 @@ int agx_fovea_fixed(agx_ctx *ctx, const void *d_action, int action_dtype, const 
             hipLaunchKernelGGL((k_fovea_fixed2<GeomR>), grid2, block, fixed2_lds(c), S(stream), gr, p);
     } else
 #endif
-        switch (c.out_mode) {
-            case AGX_OUT_RAW: LAUNCH(AGX_OUT_RAW); break;
-            case AGX_OUT_MASK: LAUNCH(AGX_OUT_MASK); break;
-            default: LAUNCH(AGX_OUT_RESIZE); break;
-        }
+        with_obs_type(ctx->obs_type, [&](auto tag) {
+            using OT = decltype(tag);
+            switch (c.out_mode) {
+                case AGX_OUT_RAW: LAUNCH(AGX_OUT_RAW); break;
+                case AGX_OUT_MASK: LAUNCH(AGX_OUT_MASK); break;
+                default: LAUNCH(AGX_OUT_RESIZE); break;
+            }
+            return 0;
+        });
 #undef LAUNCH
     AGX_HIP(ctx, hipGetLastError());
     ctx->cur_fov ^= 1;
@@ -1111,13 +1140,15 @@ int agx_step_fixed(agx_ctx *ctx, const uint8_t *d_frames, const uint8_t *d_cmd, 
     // The heterogeneous launch (ingest bands + fovea of the untouched slots in one grid, written slot after) is
     // bit-identical and measured a tie at N=1024 (69.3 vs 67.9 us per step: it fills the ingest's drain but its
     // second launch is one latency chain long), so the default is the two stand-alone launches.
-    const bool fused = ctx->tune.fused != 0;                                    // tuning / testing knob
+    const bool fused = ctx->tune.fused != 0 && ctx->obs_type == AGX_OBS_F32;   // tuning / testing knob (f32 outputs only)
     // ---- split step: the batch as P env ranges, range 0 on the caller's stream, the others on internal streams forked
     // from it and joined back before the call returns its work to the caller's stream order.  One range's fovea stores
     // and ingest drain then run under another range's ingest loads (reads and writes of the same step overlap), with
     // the results of one launch pair bit for bit (same kernels, disjoint env ranges, no shared state).
     const agx_ctx::Tune &tn = ctx->tune;
-    const bool default_forms = !fused && !tn.ingest_t && !tn.band_rows && !tn.pipe_parts && !tn.wave && !tn.pair && !tn.no_full;
+    // (the forms below write f32 observations only: a 16-bit context takes the product form)
+    const bool default_forms = !fused && !tn.ingest_t && !tn.band_rows && !tn.pipe_parts && !tn.wave && !tn.pair && !tn.no_full &&
+                               ctx->obs_type == AGX_OBS_F32;
     // Measured at N=1024 (same box, bench.py --steps 600): one launch pair 60.9 us per step; 2 parts 72.7 (69.3 with
     // low-priority internal streams, 75.1 with high), 3 parts 86.6, 4 parts 105: every cross-stream event edge costs more
     // than the overlap returns (round 1's +6-10 % came from two independent contexts that never join).  So it is opt-in.
@@ -1272,18 +1303,20 @@ int agx_fovea_peripheral(agx_ctx *ctx, const void *d_action, int action_dtype, c
     const FovParams p = fov_params(ctx, d_action, action_dtype, nullptr, d_mask, d_obs, d_fov_loc, nullptr);
     const GeomR gr{c.obs_h, c.obs_w, c.fov_h, c.fov_w};
     const bool generic_only = ctx->tune.generic != 0;                               // tuning / testing knob
+    with_obs_type(ctx->obs_type, [&](auto tag) {
+    using OT = decltype(tag);
     if (!generic_only && ctx->p3_mt && ctx->tune.per_v2 == 0) {
         const dim3 grid(c.frame_stack, c.num_envs), block(kThreads);
         const size_t lds = ctx->p3_lds;
         using GS = PGeomS<84, 84, 30, 30, 20, 20>;
         const PGeomR pg{c.obs_h, c.obs_w, c.fov_h, c.fov_w, c.per_h, c.per_w};
         const bool headline = c.obs_h == 84 && c.obs_w == 84 && c.fov_h == 30 && c.fov_w == 30 && c.per_h == 20 && c.per_w == 20;
-        if (headline && ctx->p3_mt == 12) AGX_LAUNCH(1, (k_fovea_peripheral3<GS, 12>), grid, block, lds, S(stream), GS{}, ctx->p3, p);
-        else if (headline && ctx->p3_mt == 4) AGX_LAUNCH(1, (k_fovea_peripheral3<GS, 4>), grid, block, lds, S(stream), GS{}, ctx->p3, p);
-        else if (ctx->p3_mt == 4) AGX_LAUNCH(1, (k_fovea_peripheral3<PGeomR, 4>), grid, block, lds, S(stream), pg, ctx->p3, p);
-        else if (ctx->p3_mt == 8) AGX_LAUNCH(1, (k_fovea_peripheral3<PGeomR, 8>), grid, block, lds, S(stream), pg, ctx->p3, p);
-        else if (ctx->p3_mt == 12) AGX_LAUNCH(1, (k_fovea_peripheral3<PGeomR, 12>), grid, block, lds, S(stream), pg, ctx->p3, p);
-        else AGX_LAUNCH(1, (k_fovea_peripheral3<PGeomR, 16>), grid, block, lds, S(stream), pg, ctx->p3, p);
+        if (headline && ctx->p3_mt == 12) AGX_LAUNCH(1, (k_fovea_peripheral3<GS, 12, OT>), grid, block, lds, S(stream), GS{}, ctx->p3, p);
+        else if (headline && ctx->p3_mt == 4) AGX_LAUNCH(1, (k_fovea_peripheral3<GS, 4, OT>), grid, block, lds, S(stream), GS{}, ctx->p3, p);
+        else if (ctx->p3_mt == 4) AGX_LAUNCH(1, (k_fovea_peripheral3<PGeomR, 4, OT>), grid, block, lds, S(stream), pg, ctx->p3, p);
+        else if (ctx->p3_mt == 8) AGX_LAUNCH(1, (k_fovea_peripheral3<PGeomR, 8, OT>), grid, block, lds, S(stream), pg, ctx->p3, p);
+        else if (ctx->p3_mt == 12) AGX_LAUNCH(1, (k_fovea_peripheral3<PGeomR, 12, OT>), grid, block, lds, S(stream), pg, ctx->p3, p);
+        else AGX_LAUNCH(1, (k_fovea_peripheral3<PGeomR, 16, OT>), grid, block, lds, S(stream), pg, ctx->p3, p);
     } else
     // the tuned kernel keeps A | B | C with C 16-byte aligned and one row sweep per 256 threads
     if (!generic_only && per2_lds(c) <= kMaxLds && c.per_w <= kThreads) {
@@ -1301,16 +1334,18 @@ int agx_fovea_peripheral(agx_ctx *ctx, const void *d_action, int action_dtype, c
         const size_t lds = per2_lds(c);
         // both squeeze tables are padded to their own bucket; the kernel bound must not exceed either row pitch
         const bool same_bucket = ctx->per_maxt[0] == ctx->per_maxt[1];
-        if (same_bucket && mt == 2) AGX_LAUNCH(1, k_fovea_peripheral2<2>, grid, block, lds, S(stream), g, p);
-        else if (same_bucket && mt == 4) AGX_LAUNCH(1, k_fovea_peripheral2<4>, grid, block, lds, S(stream), g, p);
-        else if (same_bucket && mt == 8) AGX_LAUNCH(1, k_fovea_peripheral2<8>, grid, block, lds, S(stream), g, p);
-        else if (same_bucket && mt == 12) AGX_LAUNCH(1, k_fovea_peripheral2<12>, grid, block, lds, S(stream), g, p);
-        else if (same_bucket && mt == 16) AGX_LAUNCH(1, k_fovea_peripheral2<16>, grid, block, lds, S(stream), g, p);
-        else AGX_LAUNCH(1, k_fovea_peripheral2<0>, grid, block, lds, S(stream), g, p);
+        if (same_bucket && mt == 2) AGX_LAUNCH(1, (k_fovea_peripheral2<2, OT>), grid, block, lds, S(stream), g, p);
+        else if (same_bucket && mt == 4) AGX_LAUNCH(1, (k_fovea_peripheral2<4, OT>), grid, block, lds, S(stream), g, p);
+        else if (same_bucket && mt == 8) AGX_LAUNCH(1, (k_fovea_peripheral2<8, OT>), grid, block, lds, S(stream), g, p);
+        else if (same_bucket && mt == 12) AGX_LAUNCH(1, (k_fovea_peripheral2<12, OT>), grid, block, lds, S(stream), g, p);
+        else if (same_bucket && mt == 16) AGX_LAUNCH(1, (k_fovea_peripheral2<16, OT>), grid, block, lds, S(stream), g, p);
+        else AGX_LAUNCH(1, (k_fovea_peripheral2<0, OT>), grid, block, lds, S(stream), g, p);
     } else {
-        hipLaunchKernelGGL((k_fovea_generic<AGX_KIND_PERIPHERAL>), dim3(c.frame_stack, c.num_envs), dim3(kThreads),
+        hipLaunchKernelGGL((k_fovea_generic<AGX_KIND_PERIPHERAL, OT>), dim3(c.frame_stack, c.num_envs), dim3(kThreads),
                            generic_lds(c), S(stream), gr, p);
     }
+    return 0;
+    });
     AGX_HIP(ctx, hipGetLastError());
     ctx->cur_fov ^= 1;
     return AGX_OK;
@@ -1329,24 +1364,26 @@ int agx_fovea_flexible(agx_ctx *ctx, const void *d_action, int action_dtype, con
     const GeomR gr{c.obs_h, c.obs_w, c.fov_h, c.fov_w};
     const bool generic_only = ctx->tune.generic != 0;                               // tuning / testing knob
     const size_t lds2 = flex2_lds(c, ctx->flex_tab_floats);
+    with_obs_type(ctx->obs_type, [&](auto tag) {
+    using OT = decltype(tag);
     if (!generic_only && ctx->f3_ok && ctx->tune.flex_v2 == 0) {
         const size_t lds3 = (size_t)ctx->f3.r0_bytes + ctx->f3.r1_bytes + (size_t)c.obs_h * sizeof(int4);
         const dim3 grid(c.frame_stack, c.num_envs), block(kThreads);
         using GS = GeomS<84, 84, 30, 30>;
         if (c.obs_h == 84 && c.obs_w == 84 && c.fov_h == 30 && c.fov_w == 30)
-            AGX_LAUNCH(1, (k_fovea_flexible3<GS>), grid, block, lds3, S(stream), GS{}, ctx->f3, p);
+            AGX_LAUNCH(1, (k_fovea_flexible3<GS, OT>), grid, block, lds3, S(stream), GS{}, ctx->f3, p);
         else
-            AGX_LAUNCH(1, (k_fovea_flexible3<GeomR>), grid, block, lds3, S(stream), gr, ctx->f3, p);
+            AGX_LAUNCH(1, (k_fovea_flexible3<GeomR, OT>), grid, block, lds3, S(stream), gr, ctx->f3, p);
     } else if (!generic_only && ctx->fr_ok && ctx->tune.flex_v2 == 0 && c.out_mode != AGX_OUT_RESIZE) {
         const dim3 grid(c.frame_stack, c.num_envs), block(kThreads);
         using GS = GeomS<84, 84, 30, 30>;
         const bool headline = c.obs_h == 84 && c.obs_w == 84 && c.fov_h == 30 && c.fov_w == 30;
         if (c.out_mode == AGX_OUT_MASK) {
-            if (headline) AGX_LAUNCH(1, (k_fovea_flexible_raw3<GS, AGX_OUT_MASK>), grid, block, ctx->fr_lds, S(stream), GS{}, ctx->fr, p);
-            else AGX_LAUNCH(1, (k_fovea_flexible_raw3<GeomR, AGX_OUT_MASK>), grid, block, ctx->fr_lds, S(stream), gr, ctx->fr, p);
+            if (headline) AGX_LAUNCH(1, (k_fovea_flexible_raw3<GS, AGX_OUT_MASK, OT>), grid, block, ctx->fr_lds, S(stream), GS{}, ctx->fr, p);
+            else AGX_LAUNCH(1, (k_fovea_flexible_raw3<GeomR, AGX_OUT_MASK, OT>), grid, block, ctx->fr_lds, S(stream), gr, ctx->fr, p);
         } else {
-            if (headline) AGX_LAUNCH(1, (k_fovea_flexible_raw3<GS, AGX_OUT_RAW>), grid, block, ctx->fr_lds, S(stream), GS{}, ctx->fr, p);
-            else AGX_LAUNCH(1, (k_fovea_flexible_raw3<GeomR, AGX_OUT_RAW>), grid, block, ctx->fr_lds, S(stream), gr, ctx->fr, p);
+            if (headline) AGX_LAUNCH(1, (k_fovea_flexible_raw3<GS, AGX_OUT_RAW, OT>), grid, block, ctx->fr_lds, S(stream), GS{}, ctx->fr, p);
+            else AGX_LAUNCH(1, (k_fovea_flexible_raw3<GeomR, AGX_OUT_RAW, OT>), grid, block, ctx->fr_lds, S(stream), gr, ctx->fr, p);
         }
     } else if (!generic_only && lds2 <= kMaxLds) {
         FlexParams g;
@@ -1357,12 +1394,14 @@ int agx_fovea_flexible(agx_ctx *ctx, const void *d_action, int action_dtype, con
             fam[k]->meta = ctx->flex_meta[k];
         }
         g.oh = c.obs_h; g.ow = c.obs_w; g.fh = c.fov_h; g.fw = c.fov_w;
-        if (c.out_mode == AGX_OUT_RESIZE) AGX_LAUNCH(1, k_fovea_flexible2<true>, dim3(c.frame_stack, c.num_envs), dim3(kThreads), lds2, S(stream), g, p);
-        else AGX_LAUNCH(1, k_fovea_flexible2<false>, dim3(c.frame_stack, c.num_envs), dim3(kThreads), lds2, S(stream), g, p);
+        if (c.out_mode == AGX_OUT_RESIZE) AGX_LAUNCH(1, (k_fovea_flexible2<true, OT>), dim3(c.frame_stack, c.num_envs), dim3(kThreads), lds2, S(stream), g, p);
+        else AGX_LAUNCH(1, (k_fovea_flexible2<false, OT>), dim3(c.frame_stack, c.num_envs), dim3(kThreads), lds2, S(stream), g, p);
     } else {
-        hipLaunchKernelGGL((k_fovea_generic<AGX_KIND_FLEXIBLE>), dim3(c.frame_stack, c.num_envs), dim3(kThreads),
+        hipLaunchKernelGGL((k_fovea_generic<AGX_KIND_FLEXIBLE, OT>), dim3(c.frame_stack, c.num_envs), dim3(kThreads),
                            generic_lds(c), S(stream), gr, p);
     }
+    return 0;
+    });
     AGX_HIP(ctx, hipGetLastError());
     ctx->cur_fov ^= 1;
     return AGX_OK;
@@ -1421,6 +1460,9 @@ int agx_fovea_flexible_packed(agx_ctx *ctx, const void *d_action, int action_dty
     if (c.kind != AGX_KIND_FLEXIBLE || c.out_mode != AGX_OUT_RAW)
         return fail(ctx, AGX_E_STATE, "agx_fovea_flexible_packed needs a flexible context in raw-crop mode (kind %d, out_mode %d)",
                     c.kind, c.out_mode);
+    if (ctx->obs_type != AGX_OBS_F32)
+        return fail(ctx, AGX_E_STATE, "agx_fovea_flexible_packed: the packed ragged crops are float32 only (context has AGX_OBS_* 0x%x)",
+                    ctx->obs_type);
     if (!d_packed || !d_offsets || capacity_floats < 0) return fail(ctx, AGX_E_INVALID, "agx_fovea_flexible_packed: null buffer");
     int rc = check_dt(ctx, d_action, action_dtype);
     if (rc) return rc;
@@ -1471,6 +1513,9 @@ int agx_step_flexible_packed(agx_ctx *ctx, const uint8_t *d_screens, int screens
     if (c.kind != AGX_KIND_FLEXIBLE || c.out_mode != AGX_OUT_RAW)
         return fail(ctx, AGX_E_STATE, "agx_step_flexible_packed needs a flexible context in raw-crop mode (kind %d, out_mode %d)",
                     c.kind, c.out_mode);
+    if (ctx->obs_type != AGX_OBS_F32)
+        return fail(ctx, AGX_E_STATE, "agx_step_flexible_packed: the packed ragged crops are float32 only (context has AGX_OBS_* 0x%x)",
+                    ctx->obs_type);
     if (!d_screens || !d_cmd || !d_packed || !d_offsets || capacity_floats < 0)
         return fail(ctx, AGX_E_INVALID, "agx_step_flexible_packed: null buffer");
     if (screens & ~(AGX_SCREENS_GRAY | AGX_SCREENS_COMPACT))

@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "agx.h"
 #include "agx_taps.h"
 
@@ -48,6 +50,19 @@ __host__ __device__ __forceinline__ float unit_fast(float k) {
     const float q = k * y;
     const float r = fmaf(-q, 255.0f, k);
     return fmaf(r, y, q);
+}
+
+// Observation element type OT (agx_config.out_mode bits AGX_OBS_*): float (the default and the reference's), __bf16 or
+// _Float16.  The arithmetic is the f32 path's whatever OT; each value is rounded to nearest-even once, at the store (bf16: a
+// plain cast, v_cvt_pk_bf16_f32; f16: v_cvt_f16_f32 in the default round-to-nearest mode with f16 denormals kept), so a
+// 16-bit observation is bit for bit the f32 observation cast to OT.  One store unit = 4 outputs: a float4 (16 B per lane)
+// at f32, 8 B per lane at 16 bits (obs4_t); the stores: store_obs in agx_k2_fixed.h, k_full in agx_k0_stack.h, lane-linear as before.
+template <class OT>
+using obs4_t = typename std::conditional<sizeof(OT) == 4, float4, uint2>::type;
+template <class OT>
+__device__ __forceinline__ uint32_t pack2(float a, float b) {
+    const OT ha = (OT)a, hb = (OT)b;
+    return (uint32_t)__builtin_bit_cast(uint16_t, ha) | ((uint32_t)__builtin_bit_cast(uint16_t, hb) << 16);
 }
 
 // Wave-uniform byte through the scalar cache.  hipcc emits a VECTOR load + s_waitcnt vmcnt(0) for

@@ -36,6 +36,8 @@ __global__ __launch_bounds__(kThreads) void k_set_stack(StackParams p) {
     reinterpret_cast<uint32_t *>(p.ring)[o] = reinterpret_cast<const uint32_t *>(p.in_u8)[o];
 }
 
+// OT: the observation element type (agx_k2_fixed.h, obs4_t): at 16 bits each lane stores its 4 outputs as 8 B, lane-linear
+template <class OT = float>
 __global__ __launch_bounds__(kThreads) void k_full(StackParams p) {
     const int n = blockIdx.z, j = blockIdx.y;
     const int i = blockIdx.x * kThreads + threadIdx.x;
@@ -50,13 +52,19 @@ __global__ __launch_bounds__(kThreads) void k_full(StackParams p) {
     o.w = unit(v >> 24);
     // write-once observation stream: written through (sc1) like the fovea kernels' (store_obs, agx_k2_fixed.h); the frame of
     // (n, j) is the buffer - wave-uniform by construction
-    const uintptr_t a = reinterpret_cast<uintptr_t>(reinterpret_cast<float4 *>(p.out_f32) + ((size_t)n * p.fs + j) * p.words);
+    const uintptr_t a = reinterpret_cast<uintptr_t>(reinterpret_cast<obs4_t<OT> *>(p.out_f32) + ((size_t)n * p.fs + j) * p.words);
     const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)a), hi = __builtin_amdgcn_readfirstlane((uint32_t)(a >> 32));
-    const __amdgpu_buffer_rsrc_t rs =
-        __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void *>(((uintptr_t)hi << 32) | lo), 0, p.words * 16, 0x00027000);
-    typedef uint32_t u4v __attribute__((ext_vector_type(4)));
-    const u4v w = {__float_as_uint(o.x), __float_as_uint(o.y), __float_as_uint(o.z), __float_as_uint(o.w)};
-    __builtin_amdgcn_raw_buffer_store_b128(w, rs, i * 16, 0, 16 /* sc1 */);
+    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void *>(((uintptr_t)hi << 32) | lo), 0,
+                                                                        p.words * (int)sizeof(obs4_t<OT>), 0x00027000);
+    if constexpr (sizeof(OT) == 2) {
+        typedef uint32_t u2v __attribute__((ext_vector_type(2)));
+        const u2v w = {pack2<OT>(o.x, o.y), pack2<OT>(o.z, o.w)};
+        __builtin_amdgcn_raw_buffer_store_b64(w, rs, i * 8, 0, 16 /* sc1 */);
+    } else {
+        typedef uint32_t u4v __attribute__((ext_vector_type(4)));
+        const u4v w = {__float_as_uint(o.x), __float_as_uint(o.y), __float_as_uint(o.z), __float_as_uint(o.w)};
+        __builtin_amdgcn_raw_buffer_store_b128(w, rs, i * 16, 0, 16 /* sc1 */);
+    }
 }
 
 }  // namespace agx

@@ -22,24 +22,33 @@ namespace agx {
 // does not: the hazard recogniser cannot see that its four data VGPRs must not be overwritten by the very next VALU
 // instruction, and the first sc1 build produced a few hundred wrong observation values per launch that way).  One buffer
 // resource per workgroup = its output frame: the pointer is wave-uniform by construction, out-of-range offsets are dropped.
+template <class OT = float>
 struct ObsOut {
     __amdgpu_buffer_rsrc_t rs;
 #ifdef AGX_CANARY_ASM_OBS_STORE
-    float4 *base;
+    obs4_t<OT> *base;
 #endif
 };
-__device__ __forceinline__ ObsOut obs_out(float4 *frame, int n_float4) {
+template <class OT = float>
+__device__ __forceinline__ ObsOut<OT> obs_out(obs4_t<OT> *frame, int n_float4) {
     const uintptr_t a = reinterpret_cast<uintptr_t>(frame);
     const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)a), hi = __builtin_amdgcn_readfirstlane((uint32_t)(a >> 32));
     void *p = reinterpret_cast<void *>(((uintptr_t)hi << 32) | lo);
-    ObsOut o;
-    o.rs = __builtin_amdgcn_make_buffer_rsrc(p, 0, n_float4 * 16, 0x00027000);
+    ObsOut<OT> o;
+    o.rs = __builtin_amdgcn_make_buffer_rsrc(p, 0, n_float4 * (int)sizeof(obs4_t<OT>), 0x00027000);
 #ifdef AGX_CANARY_ASM_OBS_STORE
     o.base = frame;
 #endif
     return o;
 }
-__device__ __forceinline__ void store_obs(const ObsOut &o, int q, const float4 &v) {
+template <class OT>
+__device__ __forceinline__ void store_obs(const ObsOut<OT> &o, int q, const float4 &v) {
+    if constexpr (sizeof(OT) == 2) {
+        // 8 B per lane, written through like the f32 store (sc1 against plain at this width)
+        typedef uint32_t u2v __attribute__((ext_vector_type(2)));
+        const u2v w = {pack2<OT>(v.x, v.y), pack2<OT>(v.z, v.w)};
+        __builtin_amdgcn_raw_buffer_store_b64(w, o.rs, q * 8, 0, 16 /* sc1 */);
+    } else {
 #ifdef AGX_CANARY_ASM_OBS_STORE
     // The KNOWN-BAD store of commit 327a14a, kept as a canary for the tests only (build.py: build_canary() ->
     // lib/libagx_canary.so, never loaded by the product): an inline-asm store is invisible to the compiler's hazard
@@ -53,23 +62,33 @@ __device__ __forceinline__ void store_obs(const ObsOut &o, int q, const float4 &
     const u4v w = {__float_as_uint(v.x), __float_as_uint(v.y), __float_as_uint(v.z), __float_as_uint(v.w)};
     __builtin_amdgcn_raw_buffer_store_b128(w, o.rs, q * 16, 0, 16 /* sc1 */);
 #endif
+    }
 }
 
 // one float of a raw crop (fixed: [fh][fw]; flexible, packed: [rh][rw] at an arbitrary 4-byte aligned offset - hence dword stores),
-// written through like the full-size observations: the crop of one stacked frame is the buffer
+// written through like the full-size observations: the crop of one stacked frame is the buffer.  16-bit OT (fixed crops only:
+// the packed ragged form is f32-only): one short per element.
+template <class OT = float>
 struct PackedOut {
     __amdgpu_buffer_rsrc_t rs;
 };
-__device__ __forceinline__ PackedOut packed_out(float *crop, int n_floats) {
+template <class OT = float>
+__device__ __forceinline__ PackedOut<OT> packed_out(OT *crop, int n_floats) {
     const uintptr_t a = reinterpret_cast<uintptr_t>(crop);
     const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)a), hi = __builtin_amdgcn_readfirstlane((uint32_t)(a >> 32));
     void *q = reinterpret_cast<void *>(((uintptr_t)hi << 32) | lo);
-    PackedOut o;
-    o.rs = __builtin_amdgcn_make_buffer_rsrc(q, 0, crop ? n_floats * 4 : 0, 0x00027000);
+    PackedOut<OT> o;
+    o.rs = __builtin_amdgcn_make_buffer_rsrc(q, 0, crop ? n_floats * (int)sizeof(OT) : 0, 0x00027000);
     return o;
 }
-__device__ __forceinline__ void store_packed(const PackedOut &o, int i, float v) {
-    __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v), o.rs, i * 4, 0, 16 /* sc1 */);
+template <class OT>
+__device__ __forceinline__ void store_packed(const PackedOut<OT> &o, int i, float v) {
+    if constexpr (sizeof(OT) == 2) {
+        const OT h = (OT)v;
+        __builtin_amdgcn_raw_buffer_store_b16(__builtin_bit_cast(uint16_t, h), o.rs, i * 2, 0, 16 /* sc1 */);
+    } else {
+        __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v), o.rs, i * 4, 0, 16 /* sc1 */);
+    }
 }
 // grid = (fs, N): workgroup (sl, n) owns PHYSICAL ring slot sl of env n, block = 256.
 // Prologue: the small state loads (action, fov_loc, head) and this thread's taps go out first; the scalar chain action ->
@@ -83,7 +102,7 @@ __device__ __forceinline__ void store_packed(const PackedOut &o, int i, float v)
 //  6.3 us, H pass with a tap load per iteration 7.3 us, row-tap loads 2.1 us of a 32.7 us launch.)
 // COHERENT: the frame is read with agent-scope loads (global_load_dword sc1: served by L2, never by this CU's L1) - for a
 // slot that the same launch has just written (k_step_env); phase 3: `head` is the pre-ingest head, every slot is processed.
-template <class G, int MODE, bool COHERENT = false>
+template <class G, int MODE, bool COHERENT = false, class OT = float>
 __device__ __forceinline__ void fovea_fixed_body(const G g, const FovParams &p, const int sl, const int n,
                                                  unsigned char *smem, const int tid) {
     constexpr int T = kThreads;
@@ -176,7 +195,7 @@ __device__ __forceinline__ void fovea_fixed_body(const G g, const FovParams &p, 
     const int xcol = tid % ow, yb = tid / ow;                         // phase-C column / first row
     const unsigned char *win = raw + c;                               // window origin inside the LDS image (row r of the frame = row 0)
     if (MODE == AGX_OUT_RAW) {
-        const PackedOut cout = packed_out(p.obs + ((size_t)n * p.fs + j) * (size_t)(fh * fw), fh * fw);
+        const auto cout = packed_out<OT>(reinterpret_cast<OT *>(p.obs) + ((size_t)n * p.fs + j) * (size_t)(fh * fw), fh * fw);
         for (int i = tid; i < fh * fw; i += kThreads) {
             const int y = i / fw, x = i - y * fw;
             store_packed(cout, i, unit_fast((float)win[y * wp + x]));
@@ -184,8 +203,8 @@ __device__ __forceinline__ void fovea_fixed_body(const G g, const FovParams &p, 
         return;
     }
     const int ow4 = ow >> 2;
-    float4 *out4 = reinterpret_cast<float4 *>(p.obs) + ((size_t)n * p.fs + j) * (size_t)(oh * ow4);
-    const ObsOut oout = obs_out(out4, oh * ow4);
+    obs4_t<OT> *out4 = reinterpret_cast<obs4_t<OT> *>(p.obs) + ((size_t)n * p.fs + j) * (size_t)(oh * ow4);
+    const auto oout = obs_out<OT>(out4, oh * ow4);
     if (MODE == AGX_OUT_MASK) {
         for (int k_ = 0; k_ < (oh * ow4 + kThreads - 1) / kThreads; ++k_) {
             const int q = tid + k_ * kThreads;
@@ -248,16 +267,16 @@ __device__ __forceinline__ void fovea_fixed_body(const G g, const FovParams &p, 
     AGX_STAMP(4);
 }
 
-template <class G, int MODE>
+template <class G, int MODE, class OT = float>
 __device__ __forceinline__ void fovea_fixed_body(const G g, const FovParams &p, const int sl, const int n,
                                                  unsigned char *smem) {
-    fovea_fixed_body<G, MODE, false>(g, p, sl, n, smem, (int)threadIdx.x);
+    fovea_fixed_body<G, MODE, false, OT>(g, p, sl, n, smem, (int)threadIdx.x);
 }
 
-template <class G, int MODE>
+template <class G, int MODE, class OT = float>
 __global__ __launch_bounds__(kThreads) void k_fovea_fixed(G g, FovParams p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    fovea_fixed_body<G, MODE>(g, p, blockIdx.x, blockIdx.y, smem);
+    fovea_fixed_body<G, MODE, OT>(g, p, blockIdx.x, blockIdx.y, smem);
 }
 
 }  // namespace agx

@@ -73,7 +73,7 @@ __device__ __forceinline__ void pass_h(const PassDesc &d, const Tap *tab, const 
 // K3: FixedFovealPeripheralEnv, K4: FlexibleFovealEnv.  grid = (fs, N), block = 256.
 // LDS: buf0, buf1 (oh*ow floats each), tab (max(oh,ow,..) taps)
 // ---------------------------------------------------------------------------------------------
-template <int KIND>
+template <int KIND, class OT = float>
 __global__ __launch_bounds__(kThreads) void k_fovea_generic(GeomR g, FovParams p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int j = blockIdx.x, n = blockIdx.y, tid = threadIdx.x;
@@ -129,8 +129,8 @@ __global__ __launch_bounds__(kThreads) void k_fovea_generic(GeomR g, FovParams p
     Tap *tab = reinterpret_cast<Tap *>(buf1 + p.buf1_floats);
     const int ow4 = ow >> 2;
     const FastDiv dv_ow4(ow4);
-    float4 *out4 = reinterpret_cast<float4 *>(p.obs) + ((size_t)n * p.fs + j) * (size_t)(oh * ow4);
-    const ObsOut oout = obs_out(out4, oh * ow4);
+    obs4_t<OT> *out4 = reinterpret_cast<obs4_t<OT> *>(p.obs) + ((size_t)n * p.fs + j) * (size_t)(oh * ow4);
+    const auto oout = obs_out<OT>(out4, oh * ow4);
 
     if (KIND == AGX_KIND_PERIPHERAL) {
         // S = full frame; periphery = expand(squeeze(S)); fovea pasted at full resolution
@@ -273,7 +273,7 @@ struct PerParams {
 // MT = compile-time bound of the squeeze passes' tap count (tables are zero-padded to it by the host);
 // MT == 0 keeps run-time trip counts.  With a fixed bound every LDS read of an output is issued before
 // the first FMA instead of one dependent read pair per tap.
-template <int MT>
+template <int MT, class OT = float>
 __global__ __launch_bounds__(kThreads) void k_fovea_peripheral2(PerParams g, FovParams p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int sl = blockIdx.x, n = blockIdx.y, tid = threadIdx.x;
@@ -341,8 +341,8 @@ __global__ __launch_bounds__(kThreads) void k_fovea_peripheral2(PerParams g, Fov
 
     const int ow4 = ow >> 2;
     const FastDiv dv_ow4(ow4), dv_pw(pw), dv_ow(ow);
-    float4 *out4 = reinterpret_cast<float4 *>(p.obs) + ((size_t)n * p.fs + j) * (size_t)(oh * ow4);
-    const ObsOut oout = obs_out(out4, oh * ow4);
+    obs4_t<OT> *out4 = reinterpret_cast<obs4_t<OT> *>(p.obs) + ((size_t)n * p.fs + j) * (size_t)(oh * ow4);
+    const auto oout = obs_out<OT>(out4, oh * ow4);
     if (!g.same) {
         // pass 0: A[y][xp] = sum_k (w0[xp][k] / 255) * raw[y][lo + k]
         // The pass-0 weights carry the 1/255 (host side), so bytes convert with v_cvt_f32_ubyteN and no
@@ -513,7 +513,7 @@ __device__ __forceinline__ float tap_dot(const LdsTab &t, int i, const float *sr
 }
 
 // RESIZE: compile-time out_mode == AGX_OUT_RESIZE (two instantiations: each keeps only the table families it reads in SGPRs)
-template <bool RESIZE>
+template <bool RESIZE, class OT = float>
 __global__ __launch_bounds__(kThreads) void k_fovea_flexible2(FlexParams g, FovParams p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int sl = blockIdx.x, n = blockIdx.y, tid = threadIdx.x;
@@ -599,8 +599,8 @@ __global__ __launch_bounds__(kThreads) void k_fovea_flexible2(FlexParams g, FovP
     const unsigned char *win = raw + r * ow + c;
     const float kInv255 = 1.0f / 255.0f;          // resampling inputs only (<= 1 ulp from k/255); pasted pixels use lut
     const int ow4 = ow >> 2;
-    float4 *out4 = reinterpret_cast<float4 *>(p.obs) + ((size_t)n * p.fs + j) * (size_t)(oh * ow4);
-    const ObsOut oout = obs_out(out4, oh * ow4);
+    obs4_t<OT> *out4 = reinterpret_cast<obs4_t<OT> *>(p.obs) + ((size_t)n * p.fs + j) * (size_t)(oh * ow4);
+    const auto oout = obs_out<OT>(out4, oh * ow4);
 
     if (squeeze) {
         // P1: A[y][xf] = Wdwn(crop)      y < rh, xf < fw

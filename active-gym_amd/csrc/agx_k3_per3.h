@@ -44,7 +44,7 @@ struct Per3Params {
     int32_t same;         // peripheral_res == obs_size: torchvision returns the input unchanged
 };
 
-template <class G, int MT>
+template <class G, int MT, class OT = float>
 __global__ __launch_bounds__(kThreads) void k_fovea_peripheral3(G g, Per3Params t, FovParams p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int sl = blockIdx.x, n = blockIdx.y, tid = threadIdx.x;
@@ -117,8 +117,8 @@ __global__ __launch_bounds__(kThreads) void k_fovea_peripheral3(G g, Per3Params 
     __syncthreads();
 
     const int ow4 = ow >> 2;
-    float4 *out4 = reinterpret_cast<float4 *>(p.obs) + ((size_t)n * p.fs + j) * (size_t)(oh * ow4);
-    const ObsOut oout = obs_out(out4, oh * ow4);
+    obs4_t<OT> *out4 = reinterpret_cast<obs4_t<OT> *>(p.obs) + ((size_t)n * p.fs + j) * (size_t)(oh * ow4);
+    const auto oout = obs_out<OT>(out4, oh * ow4);
     if (!t.same) {
         // ---- pass 0: A[y][xp] = sum_k (w0[xp][k] / 255) * raw[y][lo + k]; bytes through aligned dwords + alignbyte
         if (y00 < per0) {

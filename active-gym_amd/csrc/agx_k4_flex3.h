@@ -108,7 +108,7 @@ __device__ __forceinline__ void flex3_wcomp(const float *src, float *dst, const 
 #else
 #define AGX_K4_OCC
 #endif
-template <class G>
+template <class G, class OT = float>
 __global__ __launch_bounds__(kThreads) AGX_K4_OCC void k_fovea_flexible3(G g, Flex3Params t, FovParams p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int sl = blockIdx.x, n = blockIdx.y, tid = threadIdx.x;
@@ -283,8 +283,8 @@ __global__ __launch_bounds__(kThreads) AGX_K4_OCC void k_fovea_flexible3(G g, Fl
     // ---- out = Hfinal . E: each float4 is the 2- or 3-tap vertical blend of ds_read_b128 rows; lane-linear stores
     const int ow4 = ow >> 2;
     const float4 *E4 = reinterpret_cast<const float4 *>(E);
-    float4 *out4 = reinterpret_cast<float4 *>(p.obs) + ((size_t)n * p.fs + j) * (size_t)(oh * ow4);
-    const ObsOut oout = obs_out(out4, oh * ow4);
+    obs4_t<OT> *out4 = reinterpret_cast<obs4_t<OT> *>(p.obs) + ((size_t)n * p.fs + j) * (size_t)(oh * ow4);
+    const auto oout = obs_out<OT>(out4, oh * ow4);
     if (squeeze) {
 #pragma unroll 7
         for (int k_ = 0; k_ < (oh * ow4 + kThreads - 1) / kThreads; ++k_) {

@@ -109,7 +109,7 @@ __global__ __launch_bounds__(kThreads) void k_flex_finish_offsets(const int64_t 
     offsets[i] = i == n ? base : base + local_off[i];
 }
 
-template <class G, int OUT>
+template <class G, int OUT, class OT = float>
 __global__ __launch_bounds__(kThreads) void k_fovea_flexible_raw3(G g, FlexRawParams t, FovParams p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     constexpr bool PACKED = OUT == kRawPacked;
@@ -194,8 +194,8 @@ __global__ __launch_bounds__(kThreads) void k_fovea_flexible_raw3(G g, FlexRawPa
     float *pdst = PACKED ? p.packed + poff + (int64_t)j * cnt : nullptr;
     // packed crops are a write-once stream like the observations: written through (sc1), one buffer resource per crop
     const PackedOut pout = packed_out(pdst, cnt);
-    float4 *out4 = PACKED ? nullptr : reinterpret_cast<float4 *>(p.obs) + ((size_t)n * p.fs + j) * (size_t)(oh * ow4);
-    const ObsOut oout = obs_out(out4, oh * ow4);
+    obs4_t<OT> *out4 = PACKED ? nullptr : reinterpret_cast<obs4_t<OT> *>(p.obs) + ((size_t)n * p.fs + j) * (size_t)(oh * ow4);
+    const auto oout = obs_out<OT>(out4, oh * ow4);
     const int pr = OUT == AGX_OUT_MASK ? r : 0, pc = OUT == AGX_OUT_MASK ? c : 0;   // where the crop lands in a full frame
     const FastDiv dv_rw(rw);
 

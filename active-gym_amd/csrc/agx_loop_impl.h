@@ -22,9 +22,11 @@ __global__ __launch_bounds__(kThreads) void k_row_copy(RowCopyParams p) {
     const int64_t s = p.gather ? e : j, d = p.gather ? j : e;
     p.dst[d * p.dst_pitch16 + q] = p.src[s * p.src_pitch16 + q];
 }
-// the same gather in 4-byte words, for observation rows that are not a multiple of 16 bytes (a raw-crop context with an odd
-// fov size: fs * fov_h * fov_w floats per env); grid = (ceil(row32 / 256), k)
-__global__ __launch_bounds__(kThreads) void k_row_gather32(const uint32_t *src, const int32_t *idx, uint32_t *dst, int64_t row32) {
+// the same gather in 4-byte words (W = uint32_t), for observation rows that are not a multiple of 16 bytes (a raw-crop context
+// with an odd fov size: fs * fov_h * fov_w elements per env), or in 2-byte words (uint16_t) for 16-bit rows of odd length;
+// grid = (ceil(row32 / 256), k)
+template <class W>
+__global__ __launch_bounds__(kThreads) void k_row_gather(const W *src, const int32_t *idx, W *dst, int64_t row32) {
     const int64_t q = (int64_t)blockIdx.x * kThreads + threadIdx.x;
     if (q >= row32) return;
     const int j = blockIdx.y;
@@ -44,7 +46,8 @@ struct agx_loop {
     agx_loop_config cfg{};
     int N = 0;
     size_t screen_bytes = 0;          // one staged screen
-    size_t obs_row_floats = 0;        // one env's observation
+    size_t obs_row_floats = 0;        // one env's observation (elements)
+    size_t obs_row_bytes = 0;         // ... in bytes (elements of the context's AGX_OBS_* type)
     bool fovea = false, flexible = false;
     // step screens: two pinned sets and two device sets, alternating; the copy stream and its event edges
     uint8_t *h_frames[2] = {nullptr, nullptr}, *h_cmd[2] = {nullptr, nullptr};
@@ -137,19 +140,23 @@ int loop_reset_subset(agx_loop *l, int k, float *d_obs, int32_t *d_loc, int32_t 
     LOOP_HIP(l, hipStreamWaitEvent(st, l->ev_r[rs], 0));
     if (h2d) *h2d += (int64_t)(6 * (size_t)N + (size_t)k * l->screen_bytes);
     if (gather) {
-        if (l->obs_row_floats % 4 == 0) {
+        if (l->obs_row_bytes % 16 == 0) {
             agx::RowCopyParams q;
             q.src = reinterpret_cast<const uint4 *>(d_obs);
             q.dst = reinterpret_cast<uint4 *>(l->d_final_obs);
             q.idx = rmeta_idx(l->d_rmeta);
-            q.src_pitch16 = q.dst_pitch16 = (int64_t)(l->obs_row_floats / 4);
-            q.row16 = (int32_t)(l->obs_row_floats / 4);
+            q.src_pitch16 = q.dst_pitch16 = (int64_t)(l->obs_row_bytes / 16);
+            q.row16 = (int32_t)(l->obs_row_bytes / 16);
             q.gather = 1;
             hipLaunchKernelGGL(agx::k_row_copy, dim3((q.row16 + kThreads - 1) / kThreads, k), dim3(kThreads), 0, st, q);
-        } else {
-            const int64_t row32 = (int64_t)l->obs_row_floats;
-            hipLaunchKernelGGL(agx::k_row_gather32, dim3((unsigned)((row32 + kThreads - 1) / kThreads), k), dim3(kThreads), 0, st,
+        } else if (l->obs_row_bytes % 4 == 0) {
+            const int64_t row32 = (int64_t)(l->obs_row_bytes / 4);
+            hipLaunchKernelGGL(agx::k_row_gather<uint32_t>, dim3((unsigned)((row32 + kThreads - 1) / kThreads), k), dim3(kThreads), 0, st,
                                reinterpret_cast<const uint32_t *>(d_obs), rmeta_idx(l->d_rmeta), reinterpret_cast<uint32_t *>(l->d_final_obs), row32);
+        } else {
+            const int64_t row16 = (int64_t)(l->obs_row_bytes / 2);
+            hipLaunchKernelGGL(agx::k_row_gather<uint16_t>, dim3((unsigned)((row16 + kThreads - 1) / kThreads), k), dim3(kThreads), 0, st,
+                               reinterpret_cast<const uint16_t *>(d_obs), rmeta_idx(l->d_rmeta), reinterpret_cast<uint16_t *>(l->d_final_obs), row16);
         }
         if (l->fovea && d_loc)
             hipLaunchKernelGGL(agx::k_gather_int2, dim3((k + kThreads - 1) / kThreads), dim3(kThreads), 0, st,
@@ -231,6 +238,7 @@ int agx_loop_create(agx_ctx *ctx, const agx_host_source *src, const agx_loop_con
     int32_t dims[4];
     agx_obs_shape(ctx, dims);
     l->obs_row_floats = (size_t)dims[1] * dims[2] * dims[3];
+    l->obs_row_bytes = l->obs_row_floats * obs_elem_bytes(ctx->obs_type);
     l->fovea = c.kind != AGX_KIND_BASE;
     l->flexible = c.kind == AGX_KIND_FLEXIBLE;
     const size_t N = (size_t)l->N;
@@ -270,7 +278,7 @@ int agx_loop_create(agx_ctx *ctx, const agx_host_source *src, const agx_loop_con
     TRYL(hipStreamCreateWithFlags(&l->copy_stream, hipStreamNonBlocking));
     TRYL(hipMalloc(reinterpret_cast<void **>(&l->d_rframes), N * l->screen_bytes));
     TRYL(hipMalloc(reinterpret_cast<void **>(&l->d_rmeta), 6 * N));
-    TRYL(hipMalloc(reinterpret_cast<void **>(&l->d_final_obs), N * l->obs_row_floats * sizeof(float)));
+    TRYL(hipMalloc(reinterpret_cast<void **>(&l->d_final_obs), N * l->obs_row_bytes));
     if (l->fovea) {
         TRYL(hipMalloc(reinterpret_cast<void **>(&l->d_final_loc), N * 2 * sizeof(int32_t)));
         TRYL(hipMalloc(reinterpret_cast<void **>(&l->d_final_res), N * 2 * sizeof(int32_t)));

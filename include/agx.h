@@ -58,6 +58,17 @@ extern "C" {
 #define AGX_OUT_RESIZE  1
 #define AGX_OUT_MASK    2
 
+/* observation element type: flag bits OR-ed into agx_config.out_mode (the mode above stays in the low bits; for
+ * AGX_KIND_BASE only these bits are read).  Every value is computed in float32 as with AGX_OBS_F32 and rounded to
+ * nearest-even once, at the store: a 16-bit observation equals the f32 one converted to that type, bit for bit.  With a
+ * 16-bit context every `float *d_obs` argument below (agx_observe_full, agx_fovea_*, agx_step_fixed, agx_loop_*) points to
+ * elements of that type - the C caller casts - and agx_fovea_flexible_packed / agx_step_flexible_packed return
+ * AGX_E_STATE (the packed ragged crops are float32 only). */
+#define AGX_OBS_F32       0x00
+#define AGX_OBS_BF16      0x10
+#define AGX_OBS_F16       0x20
+#define AGX_OBS_TYPE_MASK 0x30
+
 /* sensory_action_mode (fov_env.py:114-118,193-199) */
 #define AGX_MODE_ABSOLUTE 0
 #define AGX_MODE_RELATIVE 1
@@ -98,7 +109,7 @@ typedef struct agx_config {
     int32_t frame_stack;       /* args.frame_stack (1..16)                                  */
     int32_t fov_h, fov_w;      /* args.fov_size          (ignored for AGX_KIND_BASE)        */
     int32_t per_h, per_w;      /* args.peripheral_res    (AGX_KIND_PERIPHERAL only)         */
-    int32_t out_mode;          /* AGX_OUT_*                                                 */
+    int32_t out_mode;          /* AGX_OUT_* | AGX_OBS_* (element type, default f32)         */
     int32_t action_mode;       /* AGX_MODE_*                                                */
     int32_t antialias;         /* torchvision Resize antialias (True for >= 0.17)           */
     double  sas_lo, sas_hi;    /* args.sensory_action_space, relative mode only             */
@@ -188,7 +199,7 @@ AGX_API int agx_ingest_rgb(agx_ctx *ctx, const uint8_t *d_frames, const uint8_t 
 
 /* ---- K0: base observation ----------------------------------------------
  * `np.stack(state_buffer, 0)` (atari_env.py:114,143), oldest -> newest, as
- * float32 k/255.  d_obs: f32 [N][fs][obs_h][obs_w]. */
+ * float32 k/255.  d_obs: [N][fs][obs_h][obs_w] of the context's AGX_OBS_* type (f32 by default). */
 AGX_API int agx_observe_full(agx_ctx *ctx, float *d_obs, void *stream);
 
 /* Test/checkpoint access to the stack in the same order, as u8 numerators. */
@@ -208,7 +219,7 @@ AGX_API int agx_set_fov_state(agx_ctx *ctx, const int32_t *d_fov_loc, const int3
  *   absolute: fov_loc = rint(clip(a, 0, obs - fov))
  *   relative: fov_loc = rint(clip(fov_loc + rint(clip(a, sas_lo, sas_hi)), 0, obs - fov))
  * then crop / mask-out paste / bilinear resize per out_mode.
- * d_obs     : f32, shape per agx_obs_shape
+ * d_obs     : the context's AGX_OBS_* element type (f32 by default), shape per agx_obs_shape
  * d_fov_loc : i32 [N][2] out, may be NULL          (info["fov_loc"], fov_env.py:217)
  * d_mask    : u8 [N] or NULL; envs with 0 are left untouched (state and d_obs rows). */
 AGX_API int agx_fovea_fixed(agx_ctx *ctx, const void *d_action, int action_dtype, const uint8_t *d_mask,

@@ -63,7 +63,8 @@ typedef struct agx_loop_result {
     const uint8_t *done;         /* [N] incl. life-loss terminals                                                 */
     int32_t n_done;              /* envs that ended an episode in this step                                       */
     const int32_t *done_idx;     /* [n_done] ascending                                                            */
-    const float *d_final_obs;    /* device [n_done][obs row]: their last observations (autoreset), else NULL      */
+    const float *d_final_obs;    /* device [n_done][obs row]: their last observations (autoreset), else NULL;
+                                  * elements of the context's AGX_OBS_* type                                       */
     const int32_t *d_final_loc;  /* device [n_done][2] fov_loc before the reset (fovea kinds), else NULL          */
     const int32_t *d_final_res;  /* device [n_done][2] fov_res before the reset (flexible kind), else NULL        */
     int64_t h2d_bytes;           /* bytes this call put on the copy stream                                        */
@@ -74,8 +75,8 @@ AGX_API int agx_loop_destroy(agx_loop *loop);
 AGX_API const char *agx_loop_last_error(const agx_loop *loop);
 
 /* env.reset() of every env: reset_packed(all envs, noops[N]) -> upload -> ingest (CLEAR) -> agx_fovea_reset ->
- * observation.  d_obs as the context's agx_obs_shape (agx_observe_full's for AGX_KIND_BASE); d_fov_loc / d_fov_res
- * may be NULL. */
+ * observation.  d_obs as the context's agx_obs_shape (agx_observe_full's for AGX_KIND_BASE), elements of its AGX_OBS_*
+ * type (the pointer is passed through to agx_observe_full / agx_fovea_*); d_fov_loc / d_fov_res may be NULL. */
 AGX_API int agx_loop_reset(agx_loop *loop, const int32_t *noops, float *d_obs, int32_t *d_fov_loc, int32_t *d_fov_res,
                            void *stream);
 

@@ -36,7 +36,9 @@ def one_case(k):
     native_loop = bool(rng.integers(0, 4))
     compact = bool(rng.integers(0, 4))
     chunk = int(rng.integers(0, 3))
-    cfg = dict(kind=kind, N=N, ar=ar, fs=fs, clip=clip, training=training, native=native, gray=gray, mode=mode, out=out,
+    # 16-bit outputs: each value the f32 one rounded once (bfloat16 only with device outputs: NumPy has no bfloat16)
+    obs_dtype = ["float32", "float32", "float16", "bfloat16"][int(rng.integers(0, 4 if on_device else 3))]
+    cfg = dict(obs_dtype=obs_dtype, kind=kind, N=N, ar=ar, fs=fs, clip=clip, training=training, native=native, gray=gray, mode=mode, out=out,
                n_act=n_act, lives=lives, p_life=p_life, p_over=p_over, seed=s0, on_device=on_device, native_loop=native_loop,
                compact=compact, chunk=chunk)
     kw = dict(fov_size=(30, 30), fov_init_loc=(3.5, 4.49), sensory_action_mode=mode, sensory_action_space=(-9.0, 11.0),
@@ -44,7 +46,7 @@ def one_case(k):
     src = "native" if native else (lambda a, i: LcgALE(a.seed + i, n_act, lives, p_life, p_over))
     args = AtariEnvArgs(game="g", seed=s0, obs_size=(84, 84), frame_stack=fs, action_repeat=ar, clip_reward=clip,
                         frame_source=src, frame_format="gray" if gray else "rgb", h2d_chunk_envs=chunk,
-                        device="cuda:0" if on_device else None, native_loop=native_loop, compact_rows=compact,
+                        device="cuda:0" if on_device else None, obs_dtype=obs_dtype, native_loop=native_loop, compact_rows=compact,
                         scripted_actions=n_act, scripted_lives=lives, scripted_p_life=p_life, scripted_p_over=p_over, **kw)
     env = AtariVecEnv(args, N, kind=kind, noop_fn=lambda: int(next(it_a)))
     if not on_device and rng.random() < 0.5:
@@ -75,15 +77,19 @@ def one_case(k):
         return fov.step(s, a, np.array((t,))) if kind == "flexible" else fov.step(s, a)
 
     def npy(x):
-        return x.cpu().numpy() if isinstance(x, torch.Tensor) else np.asarray(x)
+        if isinstance(x, torch.Tensor):
+            return (x.float() if x.dtype is torch.bfloat16 else x).cpu().numpy()
+        return np.asarray(x)
 
     def cmp(i, got, want, what):
-        got = npy(got)
+        got = npy(got).astype(np.float32)
         if kind == "flexible" and out == "raw":
             rh, rw = chains[i][1].fov_res
             got = got[:, :rh, :rw]
         assert got.shape == want.shape, (cfg, what, got.shape, want.shape)
-        err = float(np.abs(got - want).max())
+        # a 16-bit value is the f32 one (within TOL of the oracle) rounded to nearest: at most half an ulp more
+        rel = {"float32": 0.0, "float16": 2.0 ** -11, "bfloat16": 2.0 ** -8}[obs_dtype]
+        err = float((np.abs(got - want) - rel * np.abs(want)).max())
         assert err <= TOL, (cfg, what, i, err)
 
     obs, infos = env.reset()
