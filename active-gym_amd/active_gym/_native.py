@@ -14,12 +14,13 @@ OK, E_INVALID, E_HIP, E_NOMEM, E_STATE = 0, -1, -2, -3, -4
 KIND_BASE, KIND_FIXED, KIND_FLEXIBLE, KIND_PERIPHERAL = 0, 1, 2, 3
 OUT_RAW, OUT_RESIZE, OUT_MASK = 0, 1, 2
 OBS_F32, OBS_BF16, OBS_F16, OBS_TYPE_MASK = 0x00, 0x10, 0x20, 0x30     # element type bits of out_mode
+FRAME_RGB = 0x100                                                       # out_mode flag: three colour planes per frame
 MODE_ABSOLUTE, MODE_RELATIVE = 0, 1
 DT_F32, DT_F64, DT_I32, DT_I64 = 0, 1, 2, 3
 FOV_LOC, FOV_RES = 0, 1
 CMD_CLEAR, CMD_SKIP = 0x04, 0x08
 K_INGEST, K_FOVEA, K_FULL, K_INGEST_RGB, K_INGEST_GRAY_RAW = 1, 2, 3, 4, 5
-GRAY_CV15, GRAY_CV14 = 0, 1
+GRAY_CV15, GRAY_CV14, GRAY_NONE = 0, 1, 2     # agx_ingest_rgb; GRAY_NONE keeps the channels (FRAME_RGB)
 SCREENS_GRAY, SCREENS_COMPACT = 1, 2          # agx_step_flexible_packed: screen layout bits
 
 RAW_H, RAW_W = 210, 160

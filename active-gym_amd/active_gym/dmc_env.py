@@ -7,7 +7,10 @@ dm_control is not a dependency: ``args.frame_source`` may be a factory ``(args, 
 dm_control surface used by the reference (``reset() / step(a) -> time_step(.reward .discount .observation .last())``,
 ``physics.render(height, width, camera_id)``, ``physics.get_state()``, ``action_spec()``, ``observation_spec()``);
 by default ``dm_control.suite.load`` is used exactly as the reference does (dmc_env.py:102-108) and its absence is
-an ImportError.  Only ``from_pixels=True, grey=True`` (the reference's defaults, dmc_env.py:68-69) is built."""
+an ImportError.  Only ``from_pixels=True`` is built.  ``grey=False`` gives colour observations ``(frame_stack, 3, H, W)``, the
+shape the reference declares (dmc_env.py:119-123): the render's channels / 255, planar on the GPU (``agx_ingest_rgb`` with
+``AGX_GRAY_NONE``), every fovea operation applied to each channel plane as the gray path applies it to the gray plane (DESIGN.md
+section 4)."""
 from __future__ import annotations
 
 import os
@@ -190,11 +193,12 @@ class DMCHostRunner:
 
 class DMCVecEnv(AtariVecEnv):
     """N DMC pixel envs of one kind on one GPU; same conventions as :class:`AtariVecEnv`, continuous motor
-    actions ``(N, action_dim)`` in [-1, 1]; ``args.gray_mode`` = "cv15" (OpenCV 4.x, default) | "cv14"."""
+    actions ``(N, action_dim)`` in [-1, 1]; ``args.gray_mode`` = "cv15" (OpenCV 4.x, default) | "cv14" (gray only);
+    ``args.grey = False``: colour observations ``(N, fs, 3, H, W)``."""
 
     def _check_obs_size(self):
-        if not (getattr(self.args, "from_pixels", True) and getattr(self.args, "grey", True)):
-            raise NotImplementedError("only the reference's default from_pixels=True, grey=True DMC path is built")
+        if not getattr(self.args, "from_pixels", True):
+            raise NotImplementedError("only the reference's default from_pixels=True DMC path is built")
         if (self.obs_size[0] * self.obs_size[1]) % 4:
             raise ValueError("obs_size must have a pixel count divisible by 4")
 
@@ -216,11 +220,19 @@ class DMCVecEnv(AtariVecEnv):
             raise ValueError("gray_mode must be 'cv15' or 'cv14'")
         self._gray_mode = nat.GRAY_CV15 if mode == "cv15" else nat.GRAY_CV14
 
+    def _resolve_channels(self, args):
+        if getattr(args, "grey", True):
+            return 1
+        if getattr(args, "ragged_obs", "padded") == "packed":
+            raise ValueError("grey=False with ragged_obs='packed': the packed ragged crops are gray only")
+        return 3
+
     def _motor_space(self):
         return Box(low=-1.0, high=1.0, shape=(self.runner.action_dim,), dtype=np.float32)      # dmc_env.py:112-117
 
     def _ingest(self, cmd=None):
-        self.pipe.ingest_rgb(self._d_frames, self._d_cmd if cmd is None else cmd, self._gray_mode)
+        mode = nat.GRAY_NONE if self.channels == 3 else self._gray_mode
+        self.pipe.ingest_rgb(self._d_frames, self._d_cmd if cmd is None else cmd, mode)
 
     def _h_reset_rows(self, buf=None):
         return self._h_rframes if buf is None else buf
@@ -244,7 +256,7 @@ class DMCEnv(_SingleEnv):
         self.args = args
         self.seed_num = args.seed
         self._core = DMCVecEnv(args, 1, kind=_kind, autoreset=False)
-        self.from_pixels, self.grey = True, True
+        self.from_pixels, self.grey = True, self._core.channels == 1
         self.obs_size = self._core.obs_size
         self.camera_id = int(args.camera_id)
         self.action_repeat = self._core.action_repeat
@@ -254,7 +266,7 @@ class DMCEnv(_SingleEnv):
         self._true_action_space = Box(r.true_low, r.true_high, dtype=np.float32)
         self._norm_action_space = self._core.single_motor_space
         self.obs_dtype = self._core.obs_dtype
-        self._observation_space = Box(low=-1., high=1., shape=(self.frame_stack,) + self.obs_size,
+        self._observation_space = Box(low=-1., high=1., shape=self._core.single_observation_space.shape,   # (fs[, 3], H, W)
                                       dtype=self._core.single_observation_space.dtype)
         lo, hi = _bounds(r.envs[0].observation_spec().values(), np.float32)
         self._state_space = Box(lo, hi, dtype=np.float32)

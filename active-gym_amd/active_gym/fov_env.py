@@ -104,8 +104,9 @@ class FixedFovealEnv(_SingleEnv):
         # declared exactly as the reference declares it (fov_env.py:132-142): the flexible env inherits the
         # (fs,) + fov_size declaration for its crop mode although its crops are ragged (fov_env.py:283-286)
         crop = self._KIND != "peripheral" and not (self.mask_out or self.resize_to_full)
+        chan = (core.frame_stack, 3) if core.channels == 3 else (core.frame_stack,)        # colour DMC: (fs, 3) + ...
         self.observation_space = Box(low=-1., high=1., dtype=core.single_observation_space.dtype,
-                                     shape=(core.frame_stack,) + (tuple(self.fov_size) if crop else tuple(core.obs_size)))
+                                     shape=chan + (tuple(self.fov_size) if crop else tuple(core.obs_size)))
         self.fov_loc = np.rint(np.array(self.fov_init_loc, copy=True)).astype(np.int32)   # fov_env.py:149-150
 
     def __getattr__(self, name):
@@ -144,7 +145,7 @@ class FixedFovealEnv(_SingleEnv):
 
     def _full_state(self):
         """The wrapped env's full-frame state (what the reference's RecordWrapper sits on and records,
-        fov_env.py:59,74): float64 [fs, H, W] from the device ring.  Recording only."""
+        fov_env.py:59,74): float64 [fs, H, W] ([fs, 3, H, W] colour) from the device ring.  Recording only."""
         return self._core().pipe.observe_full()[0].cpu().numpy().astype(np.float64)
 
     def _sync(self, info):

@@ -55,10 +55,17 @@ class ObsPipeline:
                  fov_init_loc: Sequence[float] = (0, 0), sensory_action_mode: str = "absolute",
                  sensory_action_space: Optional[Sequence[float]] = None, resize_to_full: bool = False,
                  mask_out: bool = False, peripheral_res: Optional[Tuple[int, int]] = None,
-                 antialias: bool = True, device: Optional[torch.device] = None, obs_dtype=torch.float32):
+                 antialias: bool = True, device: Optional[torch.device] = None, obs_dtype=torch.float32,
+                 channels: int = 1):
         """obs_dtype: element type of every observation this pipeline writes - float32 (default), bfloat16 or float16 (a torch
-        dtype or its name).  The values are the float32 ones rounded to nearest-even once (include/agx.h, AGX_OBS_*)."""
+        dtype or its name).  The values are the float32 ones rounded to nearest-even once (include/agx.h, AGX_OBS_*).
+        channels: 1 (gray frames) or 3 (colour frames, AGX_FRAME_RGB): every frame of the stack is three planes, appended by
+        :meth:`ingest_rgb` with ``gray_mode=nat.GRAY_NONE``, and every observation / stack shape gains a channel axis after
+        the frame axis, ``(N, fs, 3, h, w)``.  Each channel goes through exactly the gray arithmetic."""
         self.obs_dtype = resolve_obs_dtype(obs_dtype)
+        if channels not in (1, 3):
+            raise ValueError(f"channels must be 1 or 3, got {channels!r}")
+        self.channels = int(channels)
         if not torch.cuda.is_available():
             raise RuntimeError("ObsPipeline needs a ROCm GPU: the observation path has no CPU implementation")
         self._lib = nat.lib()
@@ -108,13 +115,17 @@ class ObsPipeline:
         self.fov_size = (cfg.fov_h, cfg.fov_w)
         self.out_mode = cfg.out_mode
         cfg.out_mode |= obs_dtype_bits(self.obs_dtype)
+        if self.channels == 3:
+            cfg.out_mode |= nat.FRAME_RGB
         self._cfg = cfg
         self._ctx = C.c_void_p()
         nat.check(self._lib.agx_create(C.byref(cfg), C.byref(self._ctx)))
         dims = (C.c_int32 * 4)()
         nat.check(self._lib.agx_obs_shape(self._ctx, C.byref(dims)), self._ctx)
-        self.obs_shape = tuple(int(d) for d in dims)
-        self.full_shape = (self.num_envs, self.frame_stack) + self.obs_size
+        # the ABI reports {N, 3 fs, h, w} for colour: the same bytes as [N][fs][3][h][w]
+        chan = (self.frame_stack, 3) if self.channels == 3 else (self.frame_stack,)
+        self.obs_shape = (int(dims[0]),) + chan + (int(dims[2]), int(dims[3]))
+        self.full_shape = (self.num_envs,) + chan + self.obs_size
 
     # ------------------------------------------------------------------ plumbing
     def close(self):
@@ -234,9 +245,12 @@ class ObsPipeline:
         return out, loc_out
 
     # ------------------------------------------------------------------ K0
-    def ingest_rgb(self, frames: torch.Tensor, cmd: torch.Tensor, gray_mode: int = nat.GRAY_CV15):
-        """frames u8[N,obs_h,obs_w,3] obs-sized RGB renders (DMC pixel path, reference dmc_env.py:175-186):
-        cv2 BGR2GRAY fixed point -> one append to the stack."""
+    def ingest_rgb(self, frames: torch.Tensor, cmd: torch.Tensor, gray_mode: Optional[int] = None):
+        """frames u8[N,obs_h,obs_w,3] obs-sized RGB renders (DMC pixel path, reference dmc_env.py:175-186): one append to the
+        stack.  gray_mode: nat.GRAY_CV15 / GRAY_CV14 (cv2 BGR2GRAY fixed point, gray pipelines) or nat.GRAY_NONE (the three
+        channels kept, colour pipelines); None picks GRAY_CV15 or GRAY_NONE by the pipeline's channels."""
+        if gray_mode is None:
+            gray_mode = nat.GRAY_NONE if self.channels == 3 else nat.GRAY_CV15
         pf = self._chk(frames, (self.num_envs,) + self.obs_size + (3,), torch.uint8, "frames")
         pc = self._chk(cmd, (self.num_envs,), torch.uint8, "cmd")
         nat.check(self._lib.agx_ingest_rgb(self._ctx, pf, pc, int(gray_mode), self._stream()), self._ctx)

@@ -125,6 +125,7 @@ class AtariVecEnv:
         self.num_envs = int(num_envs)
         self.obs_size = tuple(int(v) for v in args.obs_size)
         self._check_obs_size()
+        self.channels = self._resolve_channels(args)     # planes per stacked frame: 1 gray, 3 colour (DMC grey=False)
         self.frame_stack = int(args.frame_stack)
         self.action_repeat = int(args.action_repeat)
         dev = getattr(args, "device", None)
@@ -158,7 +159,7 @@ class AtariVecEnv:
     def _build_pipeline(self):
         args, kind = self.args, self.kind
         kw = dict(num_envs=self.num_envs, kind=kind, obs_size=self.obs_size, frame_stack=self.frame_stack,
-                  device=self.device, obs_dtype=self.obs_dtype)
+                  device=self.device, obs_dtype=self.obs_dtype, channels=self.channels)
         if kind != "base":
             # these have no defaults in the reference and are read unconditionally (fov_env.py:110-120)
             self.fov_size = tuple(int(v) for v in args.fov_size)
@@ -188,7 +189,8 @@ class AtariVecEnv:
         kind = self.kind
         # spaces (reference atari_env.py:69-70, fov_env.py:125-142,243)
         self.single_motor_space = self._motor_space()
-        full = (self.frame_stack,) + self.obs_size
+        chan = (self.frame_stack, 3) if self.channels == 3 else (self.frame_stack,)   # colour: (fs, 3, H, W)
+        full = chan + self.obs_size
         if kind == "base":
             self.single_action_space = self.single_motor_space
             self.single_observation_space = Box(low=-1., high=1., shape=full, dtype=obs_space_dtype(self.obs_dtype))
@@ -200,7 +202,7 @@ class AtariVecEnv:
                 spaces["sensory_action_type"] = Discrete(2)
             self.single_action_space = Dict(spaces)
             crop = kind == "fixed" and not (self.mask_out or self.resize_to_full)
-            shp = (self.frame_stack,) + (self.fov_size if crop else self.obs_size)
+            shp = chan + (self.fov_size if crop else self.obs_size)
             self.single_observation_space = Box(low=-1., high=1., shape=shp, dtype=obs_space_dtype(self.obs_dtype))
         # SyncVectorEnv conventions (gymnasium<1.0): batched spaces under action_space / observation_space
         self.action_space = batch_space(self.single_action_space, self.num_envs)
@@ -245,6 +247,12 @@ class AtariVecEnv:
             # reference: cv2.resize(dsize=obs_size) yields (obs_size[1], obs_size[0]) and the assignment into
             # frame_buffer raises (atari_env.py:74,121-128)
             raise ValueError(f"obs_size {self.obs_size} must be square for Atari (cv2.resize takes (width, height))")
+
+    def _resolve_channels(self, args):
+        """Atari observations are luminance only (the reference's Atari path, atari_env.py:74): a colour request is refused."""
+        if getattr(args, "grey", True) is False or int(getattr(args, "channels", 1)) != 1:
+            raise ValueError("colour observations (grey=False) are built for the DMC envs only: the Atari path is luminance only")
+        return 1
 
     def _motor_space(self):
         return Discrete(self.runner.num_actions)

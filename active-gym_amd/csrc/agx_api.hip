@@ -12,6 +12,7 @@
 #include <new>
 #include <set>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "agx.h"
@@ -24,6 +25,7 @@ using namespace agx;
 struct agx_ctx {
     agx_config cfg;            // cfg.out_mode holds the mode only (AGX_OUT_*); its element type bits are obs_type
     int obs_type = AGX_OBS_F32;   // AGX_OBS_F32 | AGX_OBS_BF16 | AGX_OBS_F16
+    int planes = 1;               // planes per frame: 1 gray, 3 colour (AGX_FRAME_RGB); the ring holds planes * fs per env
     uint8_t *ring = nullptr;
     int32_t *head[2] = {nullptr, nullptr};
     int32_t *loc[2] = {nullptr, nullptr};
@@ -313,6 +315,12 @@ int with_obs_type(int t, F &&f) {
         default: return f(float{});
     }
 }
+// Calls f(std::integral_constant<int, NC>{}) with the context's planes per frame NC (1 gray, 3 AGX_FRAME_RGB): every launch of a
+// K0 / K2 / K3 / K4 kernel goes through this; the NC = 1 instantiations are the gray kernels as they were.
+template <class F>
+int with_planes(int planes, F &&f) {
+    return planes == 3 ? f(std::integral_constant<int, 3>{}) : f(std::integral_constant<int, 1>{});
+}
 int obs_elem_bytes(int t) { return t == AGX_OBS_F32 ? 4 : 2; }
 
 size_t fixed_lds(const agx_config &c) {
@@ -414,8 +422,10 @@ int agx_create(const agx_config *cfg, agx_ctx **out) {
     const int obs_type = cfg->out_mode & AGX_OBS_TYPE_MASK;
     if (obs_type == AGX_OBS_TYPE_MASK)
         return fail(nullptr, AGX_E_INVALID, "out_mode 0x%x: AGX_OBS_BF16 and AGX_OBS_F16 are exclusive", cfg->out_mode);
+    // AGX_FRAME_RGB: three planes per frame, stored in ctx->planes
+    const int planes = (cfg->out_mode & AGX_FRAME_RGB) ? 3 : 1;
     agx_config c_split = *cfg;
-    c_split.out_mode = cfg->out_mode & ~AGX_OBS_TYPE_MASK;
+    c_split.out_mode = cfg->out_mode & ~(AGX_OBS_TYPE_MASK | AGX_FRAME_RGB);
     const agx_config &c = c_split;
     if (c.num_envs < 1 || c.num_envs > 65535)   // env index rides on gridDim.y / gridDim.z
         return fail(nullptr, AGX_E_INVALID, "num_envs must be in [1, 65535] per context (shard larger batches)");
@@ -431,7 +441,7 @@ int agx_create(const agx_config *cfg, agx_ctx **out) {
             return fail(nullptr, AGX_E_INVALID, "fov_size (%d,%d) must be >= 1 and < obs_size (%d,%d)", c.fov_h, c.fov_w,
                         c.obs_h, c.obs_w);
         if (c.out_mode < AGX_OUT_RAW || c.out_mode > AGX_OUT_MASK)
-            return fail(nullptr, AGX_E_INVALID, "bad out_mode 0x%x (AGX_OUT_* | AGX_OBS_*)", cfg->out_mode);
+            return fail(nullptr, AGX_E_INVALID, "bad out_mode 0x%x (AGX_OUT_* | AGX_OBS_* | AGX_FRAME_RGB)", cfg->out_mode);
         if (c.action_mode != AGX_MODE_ABSOLUTE && c.action_mode != AGX_MODE_RELATIVE)
             return fail(nullptr, AGX_E_INVALID, "bad action_mode");
         if (c.action_mode == AGX_MODE_RELATIVE && !(c.sas_lo <= c.sas_hi))
@@ -457,6 +467,7 @@ int agx_create(const agx_config *cfg, agx_ctx **out) {
     if (!ctx) return fail(nullptr, AGX_E_NOMEM, "out of host memory");
     ctx->cfg = c;
     ctx->obs_type = obs_type;
+    ctx->planes = planes;
     ctx->tune.generic = env_int("AGX_FOVEA_GENERIC");
     ctx->tune.no_full = env_int("AGX_INGEST_NO_FULL");
     ctx->tune.flex_v2 = env_int("AGX_FLEX_V2");
@@ -491,8 +502,8 @@ int agx_create(const agx_config *cfg, agx_ctx **out) {
             return bail(AGX_E_HIP);                \
         }                                          \
     } while (0)
-    TRY(hipMalloc(reinterpret_cast<void **>(&ctx->ring), N * c.frame_stack * fsz));
-    TRY(hipMemset(ctx->ring, 0, N * c.frame_stack * fsz));
+    TRY(hipMalloc(reinterpret_cast<void **>(&ctx->ring), N * c.frame_stack * planes * fsz));
+    TRY(hipMemset(ctx->ring, 0, N * c.frame_stack * planes * fsz));
     for (int b = 0; b < 2; ++b) {
         TRY(hipMalloc(reinterpret_cast<void **>(&ctx->head[b]), N * sizeof(int32_t)));
         TRY(hipMemset(ctx->head[b], 0, N * sizeof(int32_t)));
@@ -694,7 +705,7 @@ int agx_obs_shape(const agx_ctx *ctx, int32_t dims[4]) {
     if (!ctx || !dims) return AGX_E_INVALID;
     const agx_config &c = ctx->cfg;
     dims[0] = c.num_envs;
-    dims[1] = c.frame_stack;
+    dims[1] = c.frame_stack * ctx->planes;
     const bool crop = c.kind == AGX_KIND_FIXED && c.out_mode == AGX_OUT_RAW;
     dims[2] = crop ? c.fov_h : c.obs_h;
     dims[3] = crop ? c.fov_w : c.obs_w;
@@ -715,14 +726,17 @@ int agx_profile_next(agx_ctx *ctx, int kernel_id, void *start_event, void *stop_
 int64_t agx_algorithmic_bytes(const agx_ctx *ctx, int kernel_id) {
     if (!ctx) return AGX_E_INVALID;
     const agx_config &c = ctx->cfg;
-    const int64_t N = c.num_envs, fs = c.frame_stack, px = (int64_t)c.obs_h * c.obs_w, e = obs_elem_bytes(ctx->obs_type);
+    const int64_t N = c.num_envs, px = (int64_t)c.obs_h * c.obs_w, e = obs_elem_bytes(ctx->obs_type);
+    const int64_t fs = (int64_t)c.frame_stack * ctx->planes;   // planes of the stack (AGX_FRAME_RGB: 3 per frame)
+    if (ctx->planes != 1 && kernel_id != AGX_K_INGEST_RGB && kernel_id != AGX_K_FULL && kernel_id != AGX_K_FOVEA)
+        return AGX_E_STATE;   // the raw-screen ingests do not run on a colour context
     switch (kernel_id) {
         case AGX_K_INGEST:   // two frames, only the source rows the vertical resize touches + one u8 slot
             return N * (2 * (int64_t)ctx->rows_touched * kRawRowBytes + px);
         case AGX_K_INGEST_GRAY_RAW:   // two gray frames, only the touched source rows, + one u8 slot
             return N * (2 * (int64_t)ctx->rows_touched * kRawW + px);
-        case AGX_K_INGEST_RGB:   // one obs-sized RGB render in, one u8 slot out
-            return N * px * 4;
+        case AGX_K_INGEST_RGB:   // one obs-sized RGB render in, one u8 slot out (colour: three u8 planes out)
+            return N * px * (3 + ctx->planes);
         case AGX_K_FULL:
             return N * fs * px * (1 + e);
         case AGX_K_FOVEA: {
@@ -738,6 +752,13 @@ int64_t agx_algorithmic_bytes(const agx_ctx *ctx, int kernel_id) {
 }
 
 // ---------------------------------------------------------------- K1
+// the entry points that do not run on a colour (AGX_FRAME_RGB) context: the raw-screen Atari ingests, the fused Atari step and
+// the packed ragged crops
+static int refuse_rgb(agx_ctx *ctx, const char *who) {
+    return fail(ctx, AGX_E_STATE, "%s: not valid on an AGX_FRAME_RGB context (colour frames come in through agx_ingest_rgb with "
+                "AGX_GRAY_NONE)", who);
+}
+
 static IngestParams ingest_params(agx_ctx *ctx, const uint8_t *d_frames, const uint8_t *d_cmd) {
     const agx_config &c = ctx->cfg;
     IngestParams p;
@@ -778,6 +799,7 @@ static size_t band12_lds(const agx_ctx *ctx) { return sizeof(int2) * (kB12Rows +
 
 int agx_ingest(agx_ctx *ctx, const uint8_t *d_frames, const uint8_t *d_cmd, void *stream) {
     if (!ctx) return AGX_E_INVALID;
+    if (ctx->planes != 1) return refuse_rgb(ctx, "agx_ingest");
     if (!d_frames || !d_cmd) return fail(ctx, AGX_E_INVALID, "agx_ingest: null buffer");
     const agx_config &c = ctx->cfg;
     if (c.obs_h != c.obs_w)
@@ -831,6 +853,7 @@ int agx_ingest(agx_ctx *ctx, const uint8_t *d_frames, const uint8_t *d_cmd, void
 
 int agx_ingest_gray_raw(agx_ctx *ctx, const uint8_t *d_gray, const uint8_t *d_cmd, void *stream) {
     if (!ctx) return AGX_E_INVALID;
+    if (ctx->planes != 1) return refuse_rgb(ctx, "agx_ingest_gray_raw");
     if (!d_gray || !d_cmd) return fail(ctx, AGX_E_INVALID, "agx_ingest_gray_raw: null buffer");
     const agx_config &c = ctx->cfg;
     if (c.obs_h != c.obs_w)
@@ -861,6 +884,7 @@ int agx_source_rows(const agx_ctx *ctx, int32_t *rows, int32_t *n) {
 // agx_ingest / agx_ingest_gray_raw from compact screens: the same band kernels with packed source rows
 static int ingest_compact(agx_ctx *ctx, const uint8_t *d_rows, const uint8_t *d_cmd, void *stream, bool gray, const char *who) {
     if (!ctx) return AGX_E_INVALID;
+    if (ctx->planes != 1) return refuse_rgb(ctx, who);
     if (!d_rows || !d_cmd) return fail(ctx, AGX_E_INVALID, "%s: null buffer", who);
     const agx_config &c = ctx->cfg;
     if (c.obs_h != c.obs_w)
@@ -897,6 +921,7 @@ int agx_ingest_gray_raw_compact(agx_ctx *ctx, const uint8_t *d_rows, const uint8
 
 int agx_ingest_gray(agx_ctx *ctx, const uint8_t *d_small, const uint8_t *d_cmd, void *stream) {
     if (!ctx) return AGX_E_INVALID;
+    if (ctx->planes != 1) return refuse_rgb(ctx, "agx_ingest_gray");
     if (!d_small || !d_cmd) return fail(ctx, AGX_E_INVALID, "agx_ingest_gray: null buffer");
     const agx_config &c = ctx->cfg;
     DeviceGuard g(c.device);
@@ -931,6 +956,22 @@ int agx_ingest_rgb(agx_ctx *ctx, const uint8_t *d_frames, const uint8_t *d_cmd, 
     p.oh = c.obs_h;
     p.ow = c.obs_w;
     p.fs = c.frame_stack;
+    if (gray_mode != AGX_GRAY_CV15 && gray_mode != AGX_GRAY_CV14 && gray_mode != AGX_GRAY_NONE)
+        return fail(ctx, AGX_E_INVALID, "agx_ingest_rgb: unknown gray_mode %d", gray_mode);
+    if ((gray_mode == AGX_GRAY_NONE) != (ctx->planes == 3))
+        return fail(ctx, AGX_E_STATE, "agx_ingest_rgb: gray_mode %d on a %s context (AGX_GRAY_NONE <=> AGX_FRAME_RGB)", gray_mode,
+                    ctx->planes == 3 ? "colour" : "gray");
+    if (gray_mode == AGX_GRAY_NONE) {
+        // colour: the three channels to three planar ring planes (k_ingest_rgb_planar), 16 pixels per thread where every plane
+        // is 16-B aligned
+        const int px = c.obs_h * c.obs_w, per = px % 16 == 0 ? 16 : 4, groups = px / per;
+        const dim3 grid((groups + kThreads - 1) / kThreads, c.num_envs);
+        if (per == 16) AGX_LAUNCH(0, k_ingest_rgb_planar<16>, grid, dim3(kThreads), 0, S(stream), p);
+        else AGX_LAUNCH(0, k_ingest_rgb_planar<4>, grid, dim3(kThreads), 0, S(stream), p);
+        AGX_HIP(ctx, hipGetLastError());
+        ctx->cur_head ^= 1;
+        return AGX_OK;
+    }
     // cv2.cvtColor(rgb, COLOR_BGR2GRAY): channel 0 gets the blue weight (dmc_env.py:181-182 hands it an RGB render)
     switch (gray_mode) {
         case AGX_GRAY_CV15: p.k0 = 3735, p.k1 = 19235, p.k2 = 9798, p.shift = 15; break;   // OpenCV 4.x: BY15 GY15 RY15
@@ -956,17 +997,21 @@ static int stack_launch(agx_ctx *ctx, int which, const uint8_t *in_u8, uint8_t *
     p.out_f32 = out_f32;
     p.words = c.obs_h * c.obs_w / 4;
     p.fs = c.frame_stack;
-    const dim3 grid((p.words + kThreads - 1) / kThreads, c.frame_stack, c.num_envs);
-    if (which == 0)
-        hipLaunchKernelGGL(k_stack_u8, grid, dim3(kThreads), 0, S(stream), p);
-    else if (which == 1)
-        hipLaunchKernelGGL(k_set_stack, grid, dim3(kThreads), 0, S(stream), p);
-    else
-        with_obs_type(ctx->obs_type, [&](auto tag) {
-            using OT = decltype(tag);
-            hipLaunchKernelGGL(k_full<OT>, grid, dim3(kThreads), 0, S(stream), p);
-            return 0;
-        });
+    const dim3 grid((p.words + kThreads - 1) / kThreads, c.frame_stack * ctx->planes, c.num_envs);
+    with_planes(ctx->planes, [&](auto pc) {
+        constexpr int NC = decltype(pc)::value;
+        if (which == 0)
+            hipLaunchKernelGGL(k_stack_u8<NC>, grid, dim3(kThreads), 0, S(stream), p);
+        else if (which == 1)
+            hipLaunchKernelGGL(k_set_stack<NC>, grid, dim3(kThreads), 0, S(stream), p);
+        else
+            with_obs_type(ctx->obs_type, [&](auto tag) {
+                using OT = decltype(tag);
+                hipLaunchKernelGGL((k_full<OT, NC>), grid, dim3(kThreads), 0, S(stream), p);
+                return 0;
+            });
+        return 0;
+    });
     AGX_HIP(ctx, hipGetLastError());
     return AGX_OK;
 }
@@ -1089,18 +1134,19 @@ int agx_fovea_fixed(agx_ctx *ctx, const void *d_action, int action_dtype, const 
     const bool headline = c.obs_h == 84 && c.obs_w == 84 && c.fov_h == 30 && c.fov_w == 30;
     using GS = GeomS<84, 84, 30, 30>;
     const GeomR gr{c.obs_h, c.obs_w, c.fov_h, c.fov_w};
-    const dim3 grid(c.frame_stack, c.num_envs), block(kThreads);
-#define LAUNCH(MODE)                                                                                  \
-    do {                                                                                              \
-        if (headline)                                                                                 \
-            AGX_LAUNCH(1, (k_fovea_fixed<GS, MODE, OT>), grid, block, lds, S(stream), GS{}, p);  \
-        else                                                                                          \
-            AGX_LAUNCH(1, (k_fovea_fixed<GeomR, MODE, OT>), grid, block, lds, S(stream), gr, p); \
+    const dim3 grid(c.frame_stack * ctx->planes, c.num_envs), block(kThreads);
+#define LAUNCH(MODE)                                                                                     \
+    do {                                                                                                 \
+        if (headline)                                                                                    \
+            AGX_LAUNCH(1, (k_fovea_fixed<GS, MODE, OT, NC>), grid, block, lds, S(stream), GS{}, p);  \
+        else                                                                                             \
+            AGX_LAUNCH(1, (k_fovea_fixed<GeomR, MODE, OT, NC>), grid, block, lds, S(stream), gr, p); \
     } while (0)
 #ifdef AGX_EXPERIMENTS
     // two physical slots per workgroup (whole launch resident at once, second frame's load hidden): measured a tie
     // with the one-slot form at N=1024 (26.3 vs 25.8 us) - the launch is store-limited
-    if (c.out_mode == AGX_OUT_RESIZE && c.frame_stack % 2 == 0 && ctx->tune.pair == 1 && ctx->obs_type == AGX_OBS_F32) {
+    if (c.out_mode == AGX_OUT_RESIZE && c.frame_stack % 2 == 0 && ctx->tune.pair == 1 && ctx->obs_type == AGX_OBS_F32 &&
+        ctx->planes == 1) {
         const dim3 grid2(c.frame_stack / 2, c.num_envs);
         if (headline)
             hipLaunchKernelGGL((k_fovea_fixed2<GS>), grid2, block, fixed2_lds(c), S(stream), GS{}, p);
@@ -1108,7 +1154,9 @@ int agx_fovea_fixed(agx_ctx *ctx, const void *d_action, int action_dtype, const 
             hipLaunchKernelGGL((k_fovea_fixed2<GeomR>), grid2, block, fixed2_lds(c), S(stream), gr, p);
     } else
 #endif
-        with_obs_type(ctx->obs_type, [&](auto tag) {
+        with_planes(ctx->planes, [&](auto pc) {
+        constexpr int NC = decltype(pc)::value;
+        return with_obs_type(ctx->obs_type, [&](auto tag) {
             using OT = decltype(tag);
             switch (c.out_mode) {
                 case AGX_OUT_RAW: LAUNCH(AGX_OUT_RAW); break;
@@ -1116,6 +1164,7 @@ int agx_fovea_fixed(agx_ctx *ctx, const void *d_action, int action_dtype, const 
                 default: LAUNCH(AGX_OUT_RESIZE); break;
             }
             return 0;
+        });
         });
 #undef LAUNCH
     AGX_HIP(ctx, hipGetLastError());
@@ -1128,6 +1177,7 @@ int agx_step_fixed(agx_ctx *ctx, const uint8_t *d_frames, const uint8_t *d_cmd, 
                    float *d_obs, int32_t *d_fov_loc, void *mid_event, void *stream) {
     if (!ctx) return AGX_E_INVALID;
     const agx_config &c = ctx->cfg;
+    if (ctx->planes != 1) return refuse_rgb(ctx, "agx_step_fixed");
     if (c.kind != AGX_KIND_FIXED) return fail(ctx, AGX_E_STATE, "agx_step_fixed on a context of kind %d", c.kind);
     if (!d_frames || !d_cmd || !d_obs) return fail(ctx, AGX_E_INVALID, "agx_step_fixed: null buffer");
     int rc = check_dt(ctx, d_action, action_dtype);
@@ -1303,20 +1353,23 @@ int agx_fovea_peripheral(agx_ctx *ctx, const void *d_action, int action_dtype, c
     const FovParams p = fov_params(ctx, d_action, action_dtype, nullptr, d_mask, d_obs, d_fov_loc, nullptr);
     const GeomR gr{c.obs_h, c.obs_w, c.fov_h, c.fov_w};
     const bool generic_only = ctx->tune.generic != 0;                               // tuning / testing knob
-    with_obs_type(ctx->obs_type, [&](auto tag) {
+    const int planes = c.frame_stack * ctx->planes;                                  // workgroups per env
+    with_planes(ctx->planes, [&](auto pc) {
+    constexpr int NC = decltype(pc)::value;
+    return with_obs_type(ctx->obs_type, [&](auto tag) {
     using OT = decltype(tag);
     if (!generic_only && ctx->p3_mt && ctx->tune.per_v2 == 0) {
-        const dim3 grid(c.frame_stack, c.num_envs), block(kThreads);
+        const dim3 grid(planes, c.num_envs), block(kThreads);
         const size_t lds = ctx->p3_lds;
         using GS = PGeomS<84, 84, 30, 30, 20, 20>;
         const PGeomR pg{c.obs_h, c.obs_w, c.fov_h, c.fov_w, c.per_h, c.per_w};
         const bool headline = c.obs_h == 84 && c.obs_w == 84 && c.fov_h == 30 && c.fov_w == 30 && c.per_h == 20 && c.per_w == 20;
-        if (headline && ctx->p3_mt == 12) AGX_LAUNCH(1, (k_fovea_peripheral3<GS, 12, OT>), grid, block, lds, S(stream), GS{}, ctx->p3, p);
-        else if (headline && ctx->p3_mt == 4) AGX_LAUNCH(1, (k_fovea_peripheral3<GS, 4, OT>), grid, block, lds, S(stream), GS{}, ctx->p3, p);
-        else if (ctx->p3_mt == 4) AGX_LAUNCH(1, (k_fovea_peripheral3<PGeomR, 4, OT>), grid, block, lds, S(stream), pg, ctx->p3, p);
-        else if (ctx->p3_mt == 8) AGX_LAUNCH(1, (k_fovea_peripheral3<PGeomR, 8, OT>), grid, block, lds, S(stream), pg, ctx->p3, p);
-        else if (ctx->p3_mt == 12) AGX_LAUNCH(1, (k_fovea_peripheral3<PGeomR, 12, OT>), grid, block, lds, S(stream), pg, ctx->p3, p);
-        else AGX_LAUNCH(1, (k_fovea_peripheral3<PGeomR, 16, OT>), grid, block, lds, S(stream), pg, ctx->p3, p);
+        if (headline && ctx->p3_mt == 12) AGX_LAUNCH(1, (k_fovea_peripheral3<GS, 12, OT, NC>), grid, block, lds, S(stream), GS{}, ctx->p3, p);
+        else if (headline && ctx->p3_mt == 4) AGX_LAUNCH(1, (k_fovea_peripheral3<GS, 4, OT, NC>), grid, block, lds, S(stream), GS{}, ctx->p3, p);
+        else if (ctx->p3_mt == 4) AGX_LAUNCH(1, (k_fovea_peripheral3<PGeomR, 4, OT, NC>), grid, block, lds, S(stream), pg, ctx->p3, p);
+        else if (ctx->p3_mt == 8) AGX_LAUNCH(1, (k_fovea_peripheral3<PGeomR, 8, OT, NC>), grid, block, lds, S(stream), pg, ctx->p3, p);
+        else if (ctx->p3_mt == 12) AGX_LAUNCH(1, (k_fovea_peripheral3<PGeomR, 12, OT, NC>), grid, block, lds, S(stream), pg, ctx->p3, p);
+        else AGX_LAUNCH(1, (k_fovea_peripheral3<PGeomR, 16, OT, NC>), grid, block, lds, S(stream), pg, ctx->p3, p);
     } else
     // the tuned kernel keeps A | B | C with C 16-byte aligned and one row sweep per 256 threads
     if (!generic_only && per2_lds(c) <= kMaxLds && c.per_w <= kThreads) {
@@ -1330,21 +1383,22 @@ int agx_fovea_peripheral(agx_ctx *ctx, const void *d_action, int action_dtype, c
         g.oh = c.obs_h; g.ow = c.obs_w; g.fh = c.fov_h; g.fw = c.fov_w; g.ph = c.per_h; g.pw = c.per_w;
         g.same = (c.per_h == c.obs_h && c.per_w == c.obs_w) ? 1 : 0;                // torchvision returns the input
         const int mt = std::max(ctx->per_maxt[0], ctx->per_maxt[1]);
-        const dim3 grid(c.frame_stack, c.num_envs), block(kThreads);
+        const dim3 grid(planes, c.num_envs), block(kThreads);
         const size_t lds = per2_lds(c);
         // both squeeze tables are padded to their own bucket; the kernel bound must not exceed either row pitch
         const bool same_bucket = ctx->per_maxt[0] == ctx->per_maxt[1];
-        if (same_bucket && mt == 2) AGX_LAUNCH(1, (k_fovea_peripheral2<2, OT>), grid, block, lds, S(stream), g, p);
-        else if (same_bucket && mt == 4) AGX_LAUNCH(1, (k_fovea_peripheral2<4, OT>), grid, block, lds, S(stream), g, p);
-        else if (same_bucket && mt == 8) AGX_LAUNCH(1, (k_fovea_peripheral2<8, OT>), grid, block, lds, S(stream), g, p);
-        else if (same_bucket && mt == 12) AGX_LAUNCH(1, (k_fovea_peripheral2<12, OT>), grid, block, lds, S(stream), g, p);
-        else if (same_bucket && mt == 16) AGX_LAUNCH(1, (k_fovea_peripheral2<16, OT>), grid, block, lds, S(stream), g, p);
-        else AGX_LAUNCH(1, (k_fovea_peripheral2<0, OT>), grid, block, lds, S(stream), g, p);
+        if (same_bucket && mt == 2) AGX_LAUNCH(1, (k_fovea_peripheral2<2, OT, NC>), grid, block, lds, S(stream), g, p);
+        else if (same_bucket && mt == 4) AGX_LAUNCH(1, (k_fovea_peripheral2<4, OT, NC>), grid, block, lds, S(stream), g, p);
+        else if (same_bucket && mt == 8) AGX_LAUNCH(1, (k_fovea_peripheral2<8, OT, NC>), grid, block, lds, S(stream), g, p);
+        else if (same_bucket && mt == 12) AGX_LAUNCH(1, (k_fovea_peripheral2<12, OT, NC>), grid, block, lds, S(stream), g, p);
+        else if (same_bucket && mt == 16) AGX_LAUNCH(1, (k_fovea_peripheral2<16, OT, NC>), grid, block, lds, S(stream), g, p);
+        else AGX_LAUNCH(1, (k_fovea_peripheral2<0, OT, NC>), grid, block, lds, S(stream), g, p);
     } else {
-        hipLaunchKernelGGL((k_fovea_generic<AGX_KIND_PERIPHERAL, OT>), dim3(c.frame_stack, c.num_envs), dim3(kThreads),
+        hipLaunchKernelGGL((k_fovea_generic<AGX_KIND_PERIPHERAL, OT, NC>), dim3(planes, c.num_envs), dim3(kThreads),
                            generic_lds(c), S(stream), gr, p);
     }
     return 0;
+    });
     });
     AGX_HIP(ctx, hipGetLastError());
     ctx->cur_fov ^= 1;
@@ -1364,26 +1418,29 @@ int agx_fovea_flexible(agx_ctx *ctx, const void *d_action, int action_dtype, con
     const GeomR gr{c.obs_h, c.obs_w, c.fov_h, c.fov_w};
     const bool generic_only = ctx->tune.generic != 0;                               // tuning / testing knob
     const size_t lds2 = flex2_lds(c, ctx->flex_tab_floats);
-    with_obs_type(ctx->obs_type, [&](auto tag) {
+    const int planes = c.frame_stack * ctx->planes;                                  // workgroups per env
+    with_planes(ctx->planes, [&](auto pc) {
+    constexpr int NC = decltype(pc)::value;
+    return with_obs_type(ctx->obs_type, [&](auto tag) {
     using OT = decltype(tag);
     if (!generic_only && ctx->f3_ok && ctx->tune.flex_v2 == 0) {
         const size_t lds3 = (size_t)ctx->f3.r0_bytes + ctx->f3.r1_bytes + (size_t)c.obs_h * sizeof(int4);
-        const dim3 grid(c.frame_stack, c.num_envs), block(kThreads);
+        const dim3 grid(planes, c.num_envs), block(kThreads);
         using GS = GeomS<84, 84, 30, 30>;
         if (c.obs_h == 84 && c.obs_w == 84 && c.fov_h == 30 && c.fov_w == 30)
-            AGX_LAUNCH(1, (k_fovea_flexible3<GS, OT>), grid, block, lds3, S(stream), GS{}, ctx->f3, p);
+            AGX_LAUNCH(1, (k_fovea_flexible3<GS, OT, NC>), grid, block, lds3, S(stream), GS{}, ctx->f3, p);
         else
-            AGX_LAUNCH(1, (k_fovea_flexible3<GeomR, OT>), grid, block, lds3, S(stream), gr, ctx->f3, p);
+            AGX_LAUNCH(1, (k_fovea_flexible3<GeomR, OT, NC>), grid, block, lds3, S(stream), gr, ctx->f3, p);
     } else if (!generic_only && ctx->fr_ok && ctx->tune.flex_v2 == 0 && c.out_mode != AGX_OUT_RESIZE) {
-        const dim3 grid(c.frame_stack, c.num_envs), block(kThreads);
+        const dim3 grid(planes, c.num_envs), block(kThreads);
         using GS = GeomS<84, 84, 30, 30>;
         const bool headline = c.obs_h == 84 && c.obs_w == 84 && c.fov_h == 30 && c.fov_w == 30;
         if (c.out_mode == AGX_OUT_MASK) {
-            if (headline) AGX_LAUNCH(1, (k_fovea_flexible_raw3<GS, AGX_OUT_MASK, OT>), grid, block, ctx->fr_lds, S(stream), GS{}, ctx->fr, p);
-            else AGX_LAUNCH(1, (k_fovea_flexible_raw3<GeomR, AGX_OUT_MASK, OT>), grid, block, ctx->fr_lds, S(stream), gr, ctx->fr, p);
+            if (headline) AGX_LAUNCH(1, (k_fovea_flexible_raw3<GS, AGX_OUT_MASK, OT, NC>), grid, block, ctx->fr_lds, S(stream), GS{}, ctx->fr, p);
+            else AGX_LAUNCH(1, (k_fovea_flexible_raw3<GeomR, AGX_OUT_MASK, OT, NC>), grid, block, ctx->fr_lds, S(stream), gr, ctx->fr, p);
         } else {
-            if (headline) AGX_LAUNCH(1, (k_fovea_flexible_raw3<GS, AGX_OUT_RAW, OT>), grid, block, ctx->fr_lds, S(stream), GS{}, ctx->fr, p);
-            else AGX_LAUNCH(1, (k_fovea_flexible_raw3<GeomR, AGX_OUT_RAW, OT>), grid, block, ctx->fr_lds, S(stream), gr, ctx->fr, p);
+            if (headline) AGX_LAUNCH(1, (k_fovea_flexible_raw3<GS, AGX_OUT_RAW, OT, NC>), grid, block, ctx->fr_lds, S(stream), GS{}, ctx->fr, p);
+            else AGX_LAUNCH(1, (k_fovea_flexible_raw3<GeomR, AGX_OUT_RAW, OT, NC>), grid, block, ctx->fr_lds, S(stream), gr, ctx->fr, p);
         }
     } else if (!generic_only && lds2 <= kMaxLds) {
         FlexParams g;
@@ -1394,13 +1451,14 @@ int agx_fovea_flexible(agx_ctx *ctx, const void *d_action, int action_dtype, con
             fam[k]->meta = ctx->flex_meta[k];
         }
         g.oh = c.obs_h; g.ow = c.obs_w; g.fh = c.fov_h; g.fw = c.fov_w;
-        if (c.out_mode == AGX_OUT_RESIZE) AGX_LAUNCH(1, (k_fovea_flexible2<true, OT>), dim3(c.frame_stack, c.num_envs), dim3(kThreads), lds2, S(stream), g, p);
-        else AGX_LAUNCH(1, (k_fovea_flexible2<false, OT>), dim3(c.frame_stack, c.num_envs), dim3(kThreads), lds2, S(stream), g, p);
+        if (c.out_mode == AGX_OUT_RESIZE) AGX_LAUNCH(1, (k_fovea_flexible2<true, OT, NC>), dim3(planes, c.num_envs), dim3(kThreads), lds2, S(stream), g, p);
+        else AGX_LAUNCH(1, (k_fovea_flexible2<false, OT, NC>), dim3(planes, c.num_envs), dim3(kThreads), lds2, S(stream), g, p);
     } else {
-        hipLaunchKernelGGL((k_fovea_generic<AGX_KIND_FLEXIBLE, OT>), dim3(c.frame_stack, c.num_envs), dim3(kThreads),
+        hipLaunchKernelGGL((k_fovea_generic<AGX_KIND_FLEXIBLE, OT, NC>), dim3(planes, c.num_envs), dim3(kThreads),
                            generic_lds(c), S(stream), gr, p);
     }
     return 0;
+    });
     });
     AGX_HIP(ctx, hipGetLastError());
     ctx->cur_fov ^= 1;
@@ -1457,6 +1515,7 @@ int agx_fovea_flexible_packed(agx_ctx *ctx, const void *d_action, int action_dty
                               int32_t *d_fov_res, void *stream) {
     if (!ctx) return AGX_E_INVALID;
     const agx_config &c = ctx->cfg;
+    if (ctx->planes != 1) return refuse_rgb(ctx, "agx_fovea_flexible_packed");
     if (c.kind != AGX_KIND_FLEXIBLE || c.out_mode != AGX_OUT_RAW)
         return fail(ctx, AGX_E_STATE, "agx_fovea_flexible_packed needs a flexible context in raw-crop mode (kind %d, out_mode %d)",
                     c.kind, c.out_mode);
@@ -1510,6 +1569,7 @@ int agx_step_flexible_packed(agx_ctx *ctx, const uint8_t *d_screens, int screens
                              int64_t *d_offsets, int32_t *d_fov_loc, int32_t *d_fov_res, void *stream) {
     if (!ctx) return AGX_E_INVALID;
     const agx_config &c = ctx->cfg;
+    if (ctx->planes != 1) return refuse_rgb(ctx, "agx_step_flexible_packed");
     if (c.kind != AGX_KIND_FLEXIBLE || c.out_mode != AGX_OUT_RAW)
         return fail(ctx, AGX_E_STATE, "agx_step_flexible_packed needs a flexible context in raw-crop mode (kind %d, out_mode %d)",
                     c.kind, c.out_mode);

@@ -16,43 +16,47 @@ struct StackParams {
     int32_t words, fs;       // words = oh*ow/4
 };
 
-// grid = (ceil(words/256), fs, N)
+// grid = (ceil(words/256), NC * fs, N).  NC = planes per frame (1: gray, 3: colour, AGX_FRAME_RGB): env n's ring holds
+// NC * fs planes, frame slot s as planes s * NC .. s * NC + NC - 1; stack-order plane y = k * NC + ch is ring plane
+// ((head + k) % fs) * NC + ch.  With NC = 1 every expression below folds to the gray form.
+template <int NC = 1>
 __global__ __launch_bounds__(kThreads) void k_stack_u8(StackParams p) {
-    const int n = blockIdx.z, j = blockIdx.y;
+    const int n = blockIdx.z, y = blockIdx.y, j = y / NC, ch = y - j * NC;
     const int i = blockIdx.x * kThreads + threadIdx.x;
     if (i >= p.words) return;
     int slot = p.head[n] + j;
     if (slot >= p.fs) slot -= p.fs;
-    const uint32_t *src = reinterpret_cast<const uint32_t *>(p.ring) + ((size_t)n * p.fs + slot) * p.words;
-    reinterpret_cast<uint32_t *>(p.out_u8)[((size_t)n * p.fs + j) * p.words + i] = src[i];
+    const uint32_t *src = reinterpret_cast<const uint32_t *>(p.ring) + (((size_t)n * p.fs + slot) * NC + ch) * p.words;
+    reinterpret_cast<uint32_t *>(p.out_u8)[((size_t)n * p.fs * NC + y) * p.words + i] = src[i];
 }
 
+template <int NC = 1>
 __global__ __launch_bounds__(kThreads) void k_set_stack(StackParams p) {
-    const int n = blockIdx.z, j = blockIdx.y;
+    const int n = blockIdx.z, y = blockIdx.y;
     const int i = blockIdx.x * kThreads + threadIdx.x;
-    if (i == 0 && j == 0) p.head[n] = 0;
+    if (i == 0 && y == 0) p.head[n] = 0;
     if (i >= p.words) return;
-    const size_t o = ((size_t)n * p.fs + j) * p.words + i;
+    const size_t o = ((size_t)n * p.fs * NC + y) * p.words + i;
     reinterpret_cast<uint32_t *>(p.ring)[o] = reinterpret_cast<const uint32_t *>(p.in_u8)[o];
 }
 
 // OT: the observation element type (agx_k2_fixed.h, obs4_t): at 16 bits each lane stores its 4 outputs as 8 B, lane-linear
-template <class OT = float>
+template <class OT = float, int NC = 1>
 __global__ __launch_bounds__(kThreads) void k_full(StackParams p) {
-    const int n = blockIdx.z, j = blockIdx.y;
+    const int n = blockIdx.z, y = blockIdx.y, j = y / NC, ch = y - j * NC;
     const int i = blockIdx.x * kThreads + threadIdx.x;
     if (i >= p.words) return;
     int slot = p.head[n] + j;
     if (slot >= p.fs) slot -= p.fs;
-    const uint32_t v = (reinterpret_cast<const uint32_t *>(p.ring) + ((size_t)n * p.fs + slot) * p.words)[i];
+    const uint32_t v = (reinterpret_cast<const uint32_t *>(p.ring) + (((size_t)n * p.fs + slot) * NC + ch) * p.words)[i];
     float4 o;
     o.x = unit(v & 0xFF);
     o.y = unit((v >> 8) & 0xFF);
     o.z = unit((v >> 16) & 0xFF);
     o.w = unit(v >> 24);
     // write-once observation stream: written through (sc1) like the fovea kernels' (store_obs, agx_k2_fixed.h); the frame of
-    // (n, j) is the buffer - wave-uniform by construction
-    const uintptr_t a = reinterpret_cast<uintptr_t>(reinterpret_cast<obs4_t<OT> *>(p.out_f32) + ((size_t)n * p.fs + j) * p.words);
+    // (n, y) is the buffer - wave-uniform by construction
+    const uintptr_t a = reinterpret_cast<uintptr_t>(reinterpret_cast<obs4_t<OT> *>(p.out_f32) + ((size_t)n * p.fs * NC + y) * p.words);
     const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)a), hi = __builtin_amdgcn_readfirstlane((uint32_t)(a >> 32));
     const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void *>(((uintptr_t)hi << 32) | lo), 0,
                                                                         p.words * (int)sizeof(obs4_t<OT>), 0x00027000);

@@ -699,4 +699,65 @@ __global__ __launch_bounds__(kThreads) void k_ingest_rgb(IngestRgbParams p) {
         for (int s = 0; s < p.fs - 1; ++s) env[(size_t)s * words + i] = 0u;
 }
 
+// K1c (colour DMC front end, AGX_FRAME_RGB + AGX_GRAY_NONE): the same append as k_ingest_rgb, but the three channels of the
+// HWC render go to three planar u8 ring planes (slot s of env n = planes 3 s .. 3 s + 2) instead of one luma plane.  Pure
+// stream, 3 B in and 3 B out per pixel.  PX pixels per thread: 16 = three 16-B loads and one 16-B store per channel (needs
+// oh * ow % 16 == 0, which keeps every plane and every env's render 16-B aligned), 4 = dwords for the other sizes.
+// Source byte 3 x + c of a thread's run is pixel x, channel c; output byte k of word w of plane c is pixel 4 w + k.
+template <int PX>
+__global__ __launch_bounds__(kThreads) void k_ingest_rgb_planar(IngestRgbParams p) {
+    constexpr int SW = PX * 3 / 4;                      // source dwords per thread
+    constexpr int OW = PX / 4;                          // output dwords per thread and plane
+    const int n = blockIdx.y;
+    const int px = p.oh * p.ow, groups = px / PX;
+    const int gi = blockIdx.x * kThreads + threadIdx.x;
+    const int i = min(gi, groups - 1);
+    // the pixel loads go out before the per-env command / head loads they do not depend on
+    uint32_t s[SW];
+    const uint32_t *src = reinterpret_cast<const uint32_t *>(p.frames) + ((size_t)n * groups + i) * SW;
+    if constexpr (PX == 16) {
+#pragma unroll
+        for (int k = 0; k < SW / 4; ++k) {
+            const uint4 v = reinterpret_cast<const uint4 *>(src)[k];
+            s[4 * k] = v.x, s[4 * k + 1] = v.y, s[4 * k + 2] = v.z, s[4 * k + 3] = v.w;
+        }
+    } else {
+#pragma unroll
+        for (int k = 0; k < SW; ++k) s[k] = src[k];
+    }
+    const uint32_t cmd = p.cmd[n];
+    const int head = p.head_in[n];
+    const bool skip = (cmd & AGX_CMD_SKIP) != 0;
+    const bool clear = (cmd & AGX_CMD_CLEAR) != 0;
+    if (blockIdx.x == 0 && threadIdx.x == 0)
+        p.head_out[n] = skip ? head : (clear ? 0 : (head + 1 == p.fs ? 0 : head + 1));
+    if (skip || gi >= groups) return;
+    const bool valid = (cmd & AGX_CMD_NVALID_MASK) != 0;
+    const int slot = clear ? p.fs - 1 : head;
+    uint8_t *env = p.ring + (size_t)n * p.fs * 3 * px;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        uint32_t o[OW];
+#pragma unroll
+        for (int w = 0; w < OW; ++w) {
+            uint32_t v = 0;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const int b = 3 * (4 * w + k) + c;      // compile-time byte index into s[]
+                v |= ((s[b >> 2] >> (8 * (b & 3))) & 0xFFu) << (8 * k);
+            }
+            o[w] = valid ? v : 0u;
+        }
+        uint32_t *dst = reinterpret_cast<uint32_t *>(env + ((size_t)slot * 3 + c) * px) + (size_t)i * OW;
+        if constexpr (PX == 16) *reinterpret_cast<uint4 *>(dst) = make_uint4(o[0], o[1], o[2], o[3]);
+        else dst[0] = o[0];
+    }
+    if (clear)
+        for (int q = 0; q < 3 * (p.fs - 1); ++q) {
+            uint32_t *dst = reinterpret_cast<uint32_t *>(env + (size_t)q * px) + (size_t)i * OW;
+            if constexpr (PX == 16) *reinterpret_cast<uint4 *>(dst) = make_uint4(0u, 0u, 0u, 0u);
+            else dst[0] = 0u;
+        }
+}
+
 }  // namespace agx

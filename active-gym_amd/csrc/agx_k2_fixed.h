@@ -102,15 +102,20 @@ __device__ __forceinline__ void store_packed(const PackedOut<OT> &o, int i, floa
 //  6.3 us, H pass with a tap load per iteration 7.3 us, row-tap loads 2.1 us of a 32.7 us launch.)
 // COHERENT: the frame is read with agent-scope loads (global_load_dword sc1: served by L2, never by this CU's L1) - for a
 // slot that the same launch has just written (k_step_env); phase 3: `head` is the pre-ingest head, every slot is processed.
-template <class G, int MODE, bool COHERENT = false, class OT = float>
-__device__ __forceinline__ void fovea_fixed_body(const G g, const FovParams &p, const int sl, const int n,
+// NC: planes per frame (1 gray, 3 colour: AGX_FRAME_RGB).  grid = (NC * fs, N); workgroup (q, n) owns ring plane q of env n,
+// i.e. channel ch = q % NC of physical slot sl = q / NC, and writes stack-order plane j * NC + ch.  The window, state and arithmetic
+// are the gray ones; only workgroup q == 0 writes the env's state.  NC = 1 folds to the gray form instruction for instruction.  The
+// fused-step phases (p.phase != 0) are gray-only.
+template <class G, int MODE, bool COHERENT = false, class OT = float, int NC = 1>
+__device__ __forceinline__ void fovea_fixed_body(const G g, const FovParams &p, const int q_, const int n,
                                                  unsigned char *smem, const int tid) {
+    const int sl = q_ / NC, ch = q_ - sl * NC;
     constexpr int T = kThreads;
     (void)T;
     AGX_STAMP(0);
     const int oh = g.oh(), ow = g.ow(), fh = g.fh(), fw = g.fw();
     if (p.mask && !p.mask[n]) {
-        if (sl == 0 && tid < 2) p.loc_out[2 * n + tid] = p.loc_in[2 * n + tid];
+        if (q_ == 0 && tid < 2) p.loc_out[2 * n + tid] = p.loc_in[2 * n + tid];
         return;
     }
     int head_fixup = 0;                      // what to add to p.head[n] to get the post-ingest head
@@ -142,7 +147,7 @@ __device__ __forceinline__ void fovea_fixed_body(const G g, const FovParams &p, 
     // life were the load chain; K2 23.1 -> 21.9 us).  Round 3 also built the narrower form - of each row only the
     // dword-aligned column span that holds [c, c + fw), 1.1 KB - and measured a tie (23.4-23.5 us both, same box): the rows of
     // a window are 84 bytes apart, so the span touches the same cache lines as the whole rows; not kept.
-    const uint32_t *fsrc = reinterpret_cast<const uint32_t *>(p.ring + ((size_t)n * p.fs + sl) * (size_t)fbytes);
+    const uint32_t *fsrc = reinterpret_cast<const uint32_t *>(p.ring + (((size_t)n * p.fs + sl) * NC + ch) * (size_t)fbytes);
     int r, c, j;
     int4 xt = make_int4(0, 0, 0, 0);                                  // this thread's column taps {lo, aux, a, b}
     const int wp = ow;                                                // row pitch of the LDS image
@@ -171,7 +176,7 @@ __device__ __forceinline__ void fovea_fixed_body(const G g, const FovParams &p, 
             const uint32_t *q = wsrc + min(tid + k * kThreads, wwords - 1);
             ww[k] = COHERENT ? __hip_atomic_load(q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : *q;
         }
-        if (sl == 0 && tid == 0) {
+        if (q_ == 0 && tid == 0) {
             p.loc_out[2 * n] = r;
             p.loc_out[2 * n + 1] = c;
             if (p.user_loc) {
@@ -195,7 +200,7 @@ __device__ __forceinline__ void fovea_fixed_body(const G g, const FovParams &p, 
     const int xcol = tid % ow, yb = tid / ow;                         // phase-C column / first row
     const unsigned char *win = raw + c;                               // window origin inside the LDS image (row r of the frame = row 0)
     if (MODE == AGX_OUT_RAW) {
-        const auto cout = packed_out<OT>(reinterpret_cast<OT *>(p.obs) + ((size_t)n * p.fs + j) * (size_t)(fh * fw), fh * fw);
+        const auto cout = packed_out<OT>(reinterpret_cast<OT *>(p.obs) + (((size_t)n * p.fs + j) * NC + ch) * (size_t)(fh * fw), fh * fw);
         for (int i = tid; i < fh * fw; i += kThreads) {
             const int y = i / fw, x = i - y * fw;
             store_packed(cout, i, unit_fast((float)win[y * wp + x]));
@@ -203,7 +208,7 @@ __device__ __forceinline__ void fovea_fixed_body(const G g, const FovParams &p, 
         return;
     }
     const int ow4 = ow >> 2;
-    obs4_t<OT> *out4 = reinterpret_cast<obs4_t<OT> *>(p.obs) + ((size_t)n * p.fs + j) * (size_t)(oh * ow4);
+    obs4_t<OT> *out4 = reinterpret_cast<obs4_t<OT> *>(p.obs) + (((size_t)n * p.fs + j) * NC + ch) * (size_t)(oh * ow4);
     const auto oout = obs_out<OT>(out4, oh * ow4);
     if (MODE == AGX_OUT_MASK) {
         for (int k_ = 0; k_ < (oh * ow4 + kThreads - 1) / kThreads; ++k_) {
@@ -267,16 +272,16 @@ __device__ __forceinline__ void fovea_fixed_body(const G g, const FovParams &p, 
     AGX_STAMP(4);
 }
 
-template <class G, int MODE, class OT = float>
+template <class G, int MODE, class OT = float, int NC = 1>
 __device__ __forceinline__ void fovea_fixed_body(const G g, const FovParams &p, const int sl, const int n,
                                                  unsigned char *smem) {
-    fovea_fixed_body<G, MODE, false, OT>(g, p, sl, n, smem, (int)threadIdx.x);
+    fovea_fixed_body<G, MODE, false, OT, NC>(g, p, sl, n, smem, (int)threadIdx.x);
 }
 
-template <class G, int MODE, class OT = float>
+template <class G, int MODE, class OT = float, int NC = 1>
 __global__ __launch_bounds__(kThreads) void k_fovea_fixed(G g, FovParams p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    fovea_fixed_body<G, MODE, OT>(g, p, blockIdx.x, blockIdx.y, smem);
+    fovea_fixed_body<G, MODE, OT, NC>(g, p, blockIdx.x, blockIdx.y, smem);
 }
 
 }  // namespace agx

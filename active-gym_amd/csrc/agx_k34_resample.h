@@ -73,14 +73,15 @@ __device__ __forceinline__ void pass_h(const PassDesc &d, const Tap *tab, const 
 // K3: FixedFovealPeripheralEnv, K4: FlexibleFovealEnv.  grid = (fs, N), block = 256.
 // LDS: buf0, buf1 (oh*ow floats each), tab (max(oh,ow,..) taps)
 // ---------------------------------------------------------------------------------------------
-template <int KIND, class OT = float>
+template <int KIND, class OT = float, int NC = 1>
 __global__ __launch_bounds__(kThreads) void k_fovea_generic(GeomR g, FovParams p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const int j = blockIdx.x, n = blockIdx.y, tid = threadIdx.x;
+    // NC: planes per frame (fovea_fixed_body); workgroup q_ writes stack-order plane q_ = j * NC + ch
+    const int q_ = blockIdx.x, j = q_ / NC, ch = q_ - j * NC, n = blockIdx.y, tid = threadIdx.x;
     const int oh = g.oh(), ow = g.ow(), fh = g.fh(), fw = g.fw();
     const bool flex = KIND == AGX_KIND_FLEXIBLE;
     if (p.mask && !p.mask[n]) {
-        if (j == 0 && tid < 2) {
+        if (q_ == 0 && tid < 2) {
             p.loc_out[2 * n + tid] = p.loc_in[2 * n + tid];
             if (flex) p.res_out[2 * n + tid] = p.res_in[2 * n + tid];
         }
@@ -103,7 +104,7 @@ __global__ __launch_bounds__(kThreads) void k_fovea_generic(GeomR g, FovParams p
     } else {
         next_loc(p, n, oh - fh, ow - fw, r, c);
     }
-    if (j == 0 && tid == 0) {
+    if (q_ == 0 && tid == 0) {
         p.loc_out[2 * n] = r;
         p.loc_out[2 * n + 1] = c;
         if (p.user_loc) {
@@ -122,14 +123,14 @@ __global__ __launch_bounds__(kThreads) void k_fovea_generic(GeomR g, FovParams p
     int slot = p.head[n] + j;
     if (slot >= p.fs) slot -= p.fs;
     const size_t fsz = (size_t)oh * ow;
-    const uint8_t *frame = p.ring + ((size_t)n * p.fs + slot) * fsz;
+    const uint8_t *frame = p.ring + (((size_t)n * p.fs + slot) * NC + ch) * fsz;
     const int cap = (oh * ow + 3) & ~3;
     float *buf0 = reinterpret_cast<float *>(smem);
     float *buf1 = buf0 + cap;
     Tap *tab = reinterpret_cast<Tap *>(buf1 + p.buf1_floats);
     const int ow4 = ow >> 2;
     const FastDiv dv_ow4(ow4);
-    obs4_t<OT> *out4 = reinterpret_cast<obs4_t<OT> *>(p.obs) + ((size_t)n * p.fs + j) * (size_t)(oh * ow4);
+    obs4_t<OT> *out4 = reinterpret_cast<obs4_t<OT> *>(p.obs) + (((size_t)n * p.fs + j) * NC + ch) * (size_t)(oh * ow4);
     const auto oout = obs_out<OT>(out4, oh * ow4);
 
     if (KIND == AGX_KIND_PERIPHERAL) {
@@ -273,13 +274,13 @@ struct PerParams {
 // MT = compile-time bound of the squeeze passes' tap count (tables are zero-padded to it by the host);
 // MT == 0 keeps run-time trip counts.  With a fixed bound every LDS read of an output is issued before
 // the first FMA instead of one dependent read pair per tap.
-template <int MT, class OT = float>
+template <int MT, class OT = float, int NC = 1>
 __global__ __launch_bounds__(kThreads) void k_fovea_peripheral2(PerParams g, FovParams p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const int sl = blockIdx.x, n = blockIdx.y, tid = threadIdx.x;
+    const int q_ = blockIdx.x, sl = q_ / NC, ch = q_ - sl * NC, n = blockIdx.y, tid = threadIdx.x;   // NC: see fovea_fixed_body
     const int oh = g.oh, ow = g.ow, fh = g.fh, fw = g.fw, ph = g.ph, pw = g.pw;
     if (p.mask && !p.mask[n]) {
-        if (sl == 0 && tid < 2) p.loc_out[2 * n + tid] = p.loc_in[2 * n + tid];
+        if (q_ == 0 && tid < 2) p.loc_out[2 * n + tid] = p.loc_in[2 * n + tid];
         return;
     }
     constexpr int MTR = MT > 0 ? MT : 1;
@@ -298,7 +299,7 @@ __global__ __launch_bounds__(kThreads) void k_fovea_peripheral2(PerParams g, Fov
 
     // ---- every round trip starts now: the frame, this thread's pass-0 / pass-2 taps (registers), the
     // pass-1 / pass-3 tables (-> LDS), then the small state loads
-    const uint32_t *fsrc = reinterpret_cast<const uint32_t *>(p.ring + ((size_t)n * p.fs + sl) * (size_t)fbytes);
+    const uint32_t *fsrc = reinterpret_cast<const uint32_t *>(p.ring + (((size_t)n * p.fs + sl) * NC + ch) * (size_t)fbytes);
     constexpr int kFW = 7;
     uint32_t fw_[kFW];
 #pragma unroll
@@ -325,7 +326,7 @@ __global__ __launch_bounds__(kThreads) void k_fovea_peripheral2(PerParams g, Fov
     compute_loc(p, lin, oh - fh, ow - fw, r, c);
     int j = sl - head;
     if (j < 0) j += p.fs;
-    if (sl == 0 && tid == 0) {
+    if (q_ == 0 && tid == 0) {
         p.loc_out[2 * n] = r;
         p.loc_out[2 * n + 1] = c;
         if (p.user_loc) {
@@ -341,7 +342,7 @@ __global__ __launch_bounds__(kThreads) void k_fovea_peripheral2(PerParams g, Fov
 
     const int ow4 = ow >> 2;
     const FastDiv dv_ow4(ow4), dv_pw(pw), dv_ow(ow);
-    obs4_t<OT> *out4 = reinterpret_cast<obs4_t<OT> *>(p.obs) + ((size_t)n * p.fs + j) * (size_t)(oh * ow4);
+    obs4_t<OT> *out4 = reinterpret_cast<obs4_t<OT> *>(p.obs) + (((size_t)n * p.fs + j) * NC + ch) * (size_t)(oh * ow4);
     const auto oout = obs_out<OT>(out4, oh * ow4);
     if (!g.same) {
         // pass 0: A[y][xp] = sum_k (w0[xp][k] / 255) * raw[y][lo + k]
@@ -513,13 +514,13 @@ __device__ __forceinline__ float tap_dot(const LdsTab &t, int i, const float *sr
 }
 
 // RESIZE: compile-time out_mode == AGX_OUT_RESIZE (two instantiations: each keeps only the table families it reads in SGPRs)
-template <bool RESIZE, class OT = float>
+template <bool RESIZE, class OT = float, int NC = 1>
 __global__ __launch_bounds__(kThreads) void k_fovea_flexible2(FlexParams g, FovParams p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const int sl = blockIdx.x, n = blockIdx.y, tid = threadIdx.x;
+    const int q_ = blockIdx.x, sl = q_ / NC, ch = q_ - sl * NC, n = blockIdx.y, tid = threadIdx.x;   // NC: see fovea_fixed_body
     const int oh = g.oh, ow = g.ow, fh = g.fh, fw = g.fw;
     if (p.mask && !p.mask[n]) {
-        if (sl == 0 && tid < 2) {
+        if (q_ == 0 && tid < 2) {
             p.loc_out[2 * n + tid] = p.loc_in[2 * n + tid];
             p.res_out[2 * n + tid] = p.res_in[2 * n + tid];
         }
@@ -539,7 +540,7 @@ __global__ __launch_bounds__(kThreads) void k_fovea_flexible2(FlexParams g, FovP
     float *tabs = B + ((fh * fw + 3) & ~3);
 
     // ---- round trips start now
-    const uint32_t *fsrc = reinterpret_cast<const uint32_t *>(p.ring + ((size_t)n * p.fs + sl) * (size_t)fbytes);
+    const uint32_t *fsrc = reinterpret_cast<const uint32_t *>(p.ring + (((size_t)n * p.fs + sl) * NC + ch) * (size_t)fbytes);
     constexpr int kFW = 7;
     uint32_t fw_[kFW];
 #pragma unroll
@@ -561,7 +562,7 @@ __global__ __launch_bounds__(kThreads) void k_fovea_flexible2(FlexParams g, FovP
     }
     int j = sl - head;
     if (j < 0) j += p.fs;
-    if (sl == 0 && tid == 0) {
+    if (q_ == 0 && tid == 0) {
         p.loc_out[2 * n] = r;
         p.loc_out[2 * n + 1] = c;
         p.res_out[2 * n] = rh;
@@ -599,7 +600,7 @@ __global__ __launch_bounds__(kThreads) void k_fovea_flexible2(FlexParams g, FovP
     const unsigned char *win = raw + r * ow + c;
     const float kInv255 = 1.0f / 255.0f;          // resampling inputs only (<= 1 ulp from k/255); pasted pixels use lut
     const int ow4 = ow >> 2;
-    obs4_t<OT> *out4 = reinterpret_cast<obs4_t<OT> *>(p.obs) + ((size_t)n * p.fs + j) * (size_t)(oh * ow4);
+    obs4_t<OT> *out4 = reinterpret_cast<obs4_t<OT> *>(p.obs) + (((size_t)n * p.fs + j) * NC + ch) * (size_t)(oh * ow4);
     const auto oout = obs_out<OT>(out4, oh * ow4);
 
     if (squeeze) {

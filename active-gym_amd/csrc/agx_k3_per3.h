@@ -44,13 +44,13 @@ struct Per3Params {
     int32_t same;         // peripheral_res == obs_size: torchvision returns the input unchanged
 };
 
-template <class G, int MT, class OT = float>
+template <class G, int MT, class OT = float, int NC = 1>
 __global__ __launch_bounds__(kThreads) void k_fovea_peripheral3(G g, Per3Params t, FovParams p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const int sl = blockIdx.x, n = blockIdx.y, tid = threadIdx.x;
+    const int q_ = blockIdx.x, sl = q_ / NC, ch = q_ - sl * NC, n = blockIdx.y, tid = threadIdx.x;   // NC: see fovea_fixed_body
     const int oh = g.oh(), ow = g.ow(), fh = g.fh(), fw = g.fw(), ph = g.ph(), pw = g.pw();
     if (p.mask && !p.mask[n]) {
-        if (sl == 0 && tid < 2) p.loc_out[2 * n + tid] = p.loc_in[2 * n + tid];
+        if (q_ == 0 && tid < 2) p.loc_out[2 * n + tid] = p.loc_in[2 * n + tid];
         return;
     }
     const int fbytes = oh * ow, fwords = fbytes >> 2;
@@ -69,7 +69,7 @@ __global__ __launch_bounds__(kThreads) void k_fovea_peripheral3(G g, Per3Params 
     // ---- every round trip starts now: state, the frame, this thread's taps
     int head;
     const LocIn lin = load_loc_inputs_scalar(p, n, p.head, head);
-    const uint32_t *fsrc = reinterpret_cast<const uint32_t *>(p.ring + ((size_t)n * p.fs + sl) * (size_t)fbytes);
+    const uint32_t *fsrc = reinterpret_cast<const uint32_t *>(p.ring + (((size_t)n * p.fs + sl) * NC + ch) * (size_t)fbytes);
     constexpr int kFW = 7;
     uint32_t fw_[kFW];
 #pragma unroll
@@ -95,7 +95,7 @@ __global__ __launch_bounds__(kThreads) void k_fovea_peripheral3(G g, Per3Params 
     c = __builtin_amdgcn_readfirstlane(c);
     int j = sl - __builtin_amdgcn_readfirstlane(head);
     if (j < 0) j += p.fs;
-    if (sl == 0 && tid == 0) {
+    if (q_ == 0 && tid == 0) {
         p.loc_out[2 * n] = r;
         p.loc_out[2 * n + 1] = c;
         if (p.user_loc) {
@@ -117,7 +117,7 @@ __global__ __launch_bounds__(kThreads) void k_fovea_peripheral3(G g, Per3Params 
     __syncthreads();
 
     const int ow4 = ow >> 2;
-    obs4_t<OT> *out4 = reinterpret_cast<obs4_t<OT> *>(p.obs) + ((size_t)n * p.fs + j) * (size_t)(oh * ow4);
+    obs4_t<OT> *out4 = reinterpret_cast<obs4_t<OT> *>(p.obs) + (((size_t)n * p.fs + j) * NC + ch) * (size_t)(oh * ow4);
     const auto oout = obs_out<OT>(out4, oh * ow4);
     if (!t.same) {
         // ---- pass 0: A[y][xp] = sum_k (w0[xp][k] / 255) * raw[y][lo + k]; bytes through aligned dwords + alignbyte

@@ -108,13 +108,13 @@ __device__ __forceinline__ void flex3_wcomp(const float *src, float *dst, const 
 #else
 #define AGX_K4_OCC
 #endif
-template <class G, class OT = float>
+template <class G, class OT = float, int NC = 1>
 __global__ __launch_bounds__(kThreads) AGX_K4_OCC void k_fovea_flexible3(G g, Flex3Params t, FovParams p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const int sl = blockIdx.x, n = blockIdx.y, tid = threadIdx.x;
+    const int q_ = blockIdx.x, sl = q_ / NC, ch = q_ - sl * NC, n = blockIdx.y, tid = threadIdx.x;   // NC: see fovea_fixed_body
     const int oh = g.oh(), ow = g.ow(), fh = g.fh();
     if (p.mask && !p.mask[n]) {
-        if (sl == 0 && tid < 2) {
+        if (q_ == 0 && tid < 2) {
             p.loc_out[2 * n + tid] = p.loc_in[2 * n + tid];
             p.res_out[2 * n + tid] = p.res_in[2 * n + tid];
         }
@@ -130,7 +130,7 @@ __global__ __launch_bounds__(kThreads) AGX_K4_OCC void k_fovea_flexible3(G g, Fl
     int head, type;
     int2 res_old;
     const LocIn lin = load_flex_inputs_scalar(p, n, head, res_old, type);     // through the scalar cache: a shorter first hop
-    const uint32_t *fsrc = reinterpret_cast<const uint32_t *>(p.ring + ((size_t)n * p.fs + sl) * (size_t)fbytes);
+    const uint32_t *fsrc = reinterpret_cast<const uint32_t *>(p.ring + (((size_t)n * p.fs + sl) * NC + ch) * (size_t)fbytes);
 
     // ---- state update (fov_env.py:300-324); res from agx_set_fov_state is clamped for memory safety only
     int rh = min(max(res_old.x, 1), oh), rw = min(max(res_old.y, 1), ow), r, c;
@@ -149,7 +149,7 @@ __global__ __launch_bounds__(kThreads) AGX_K4_OCC void k_fovea_flexible3(G g, Fl
     c = __builtin_amdgcn_readfirstlane(c);
     int j = sl - __builtin_amdgcn_readfirstlane(head);
     if (j < 0) j += p.fs;
-    if (sl == 0 && tid == 0) {
+    if (q_ == 0 && tid == 0) {
         p.loc_out[2 * n] = r;
         p.loc_out[2 * n + 1] = c;
         p.res_out[2 * n] = rh;
@@ -283,7 +283,7 @@ __global__ __launch_bounds__(kThreads) AGX_K4_OCC void k_fovea_flexible3(G g, Fl
     // ---- out = Hfinal . E: each float4 is the 2- or 3-tap vertical blend of ds_read_b128 rows; lane-linear stores
     const int ow4 = ow >> 2;
     const float4 *E4 = reinterpret_cast<const float4 *>(E);
-    obs4_t<OT> *out4 = reinterpret_cast<obs4_t<OT> *>(p.obs) + ((size_t)n * p.fs + j) * (size_t)(oh * ow4);
+    obs4_t<OT> *out4 = reinterpret_cast<obs4_t<OT> *>(p.obs) + (((size_t)n * p.fs + j) * NC + ch) * (size_t)(oh * ow4);
     const auto oout = obs_out<OT>(out4, oh * ow4);
     if (squeeze) {
 #pragma unroll 7

@@ -109,14 +109,15 @@ __global__ __launch_bounds__(kThreads) void k_flex_finish_offsets(const int64_t 
     offsets[i] = i == n ? base : base + local_off[i];
 }
 
-template <class G, int OUT, class OT = float>
+template <class G, int OUT, class OT = float, int NC = 1>
 __global__ __launch_bounds__(kThreads) void k_fovea_flexible_raw3(G g, FlexRawParams t, FovParams p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     constexpr bool PACKED = OUT == kRawPacked;
-    const int sl = blockIdx.x, n = blockIdx.y, tid = threadIdx.x;
+    static_assert(!PACKED || NC == 1, "the packed ragged crops are gray only");
+    const int q_ = blockIdx.x, sl = q_ / NC, ch = q_ - sl * NC, n = blockIdx.y, tid = threadIdx.x;   // NC: see fovea_fixed_body
     const int oh = g.oh(), ow = g.ow(), fh = g.fh();
     if (!PACKED && p.mask && !p.mask[n]) {
-        if (sl == 0 && tid < 2) {
+        if (q_ == 0 && tid < 2) {
             p.loc_out[2 * n + tid] = p.loc_in[2 * n + tid];
             p.res_out[2 * n + tid] = p.res_in[2 * n + tid];
         }
@@ -155,7 +156,7 @@ __global__ __launch_bounds__(kThreads) void k_fovea_flexible_raw3(G g, FlexRawPa
         head = __builtin_amdgcn_readfirstlane(hd);
         poff = ((int64_t)__builtin_amdgcn_readfirstlane((int)(off >> 32)) << 32) |
                (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)off);
-        if (sl == 0 && tid == 0) {
+        if (q_ == 0 && tid == 0) {
             t.offsets[n] = poff;
             if (n == t.n_envs - 1) t.offsets[n + 1] = poff + (int64_t)p.fs * rh * rw;
         }
@@ -177,7 +178,7 @@ __global__ __launch_bounds__(kThreads) void k_fovea_flexible_raw3(G g, FlexRawPa
         r = __builtin_amdgcn_readfirstlane(r);
         c = __builtin_amdgcn_readfirstlane(c);
         head = __builtin_amdgcn_readfirstlane(head);
-        if (sl == 0 && tid == 0) {
+        if (q_ == 0 && tid == 0) {
             *reinterpret_cast<int2 *>(p.loc_out + 2 * n) = make_int2(r, c);
             *reinterpret_cast<int2 *>(p.res_out + 2 * n) = make_int2(rh, rw);
             if (p.user_loc) *reinterpret_cast<int2 *>(p.user_loc + 2 * n) = make_int2(r, c);
@@ -189,12 +190,12 @@ __global__ __launch_bounds__(kThreads) void k_fovea_flexible_raw3(G g, FlexRawPa
     const int cnt = rh * rw;
     if (PACKED && poff + (int64_t)p.fs * cnt > p.packed_cap) return;   // the caller's buffer is too small for this env
     const bool squeeze = rh > fh;                                     // rows only, fov_env.py:286
-    const uint8_t *frame = p.ring + ((size_t)n * p.fs + sl) * (size_t)fbytes;
+    const uint8_t *frame = p.ring + (((size_t)n * p.fs + sl) * NC + ch) * (size_t)fbytes;
     const int ow4 = ow >> 2;
     float *pdst = PACKED ? p.packed + poff + (int64_t)j * cnt : nullptr;
     // packed crops are a write-once stream like the observations: written through (sc1), one buffer resource per crop
     const PackedOut pout = packed_out(pdst, cnt);
-    obs4_t<OT> *out4 = PACKED ? nullptr : reinterpret_cast<obs4_t<OT> *>(p.obs) + ((size_t)n * p.fs + j) * (size_t)(oh * ow4);
+    obs4_t<OT> *out4 = PACKED ? nullptr : reinterpret_cast<obs4_t<OT> *>(p.obs) + (((size_t)n * p.fs + j) * NC + ch) * (size_t)(oh * ow4);
     const auto oout = obs_out<OT>(out4, oh * ow4);
     const int pr = OUT == AGX_OUT_MASK ? r : 0, pc = OUT == AGX_OUT_MASK ? c : 0;   // where the crop lands in a full frame
     const FastDiv dv_rw(rw);

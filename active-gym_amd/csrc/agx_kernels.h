@@ -4,6 +4,7 @@
 //   k_ingest            K1  RGB -> ALE luminance -> OpenCV fixed-point bilinear -> 2-frame max -> u8 ring slot
 //   k_ingest_gray       K1' same append from already obs-sized gray frames
 //   k_ingest_rgb        K1b DMC front end: obs-sized RGB -> cv2 BGR2GRAY fixed point -> ring slot (no max, no resize)
+//   k_ingest_rgb_planar K1c colour DMC front end (AGX_FRAME_RGB): obs-sized RGB -> three planar ring planes
 //   k_stack_u8 / k_full K0  ring -> stack order (u8 / f32 k/255)
 //   k_fovea_fixed       K2  clip/rint sensory action, crop, {raw | mask-out | bilinear upsample}
 //   k_fovea_generic     K3/K4 peripheral squeeze-expand + paste, flexible (ragged) fovea

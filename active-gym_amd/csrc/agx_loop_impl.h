@@ -220,6 +220,8 @@ int agx_loop_destroy(agx_loop *l) {
 
 int agx_loop_create(agx_ctx *ctx, const agx_host_source *src, const agx_loop_config *cfg, agx_loop **out) {
     if (!ctx || !src || !cfg || !out) return lfail(nullptr, AGX_E_INVALID, "agx_loop_create: null argument");
+    if (ctx->planes != 1)
+        return lfail(nullptr, AGX_E_STATE, "agx_loop_create: the native loop runs Atari screens; an AGX_FRAME_RGB context has none");
     *out = nullptr;
     if (cfg->struct_size != (int32_t)sizeof(agx_loop_config))
         return lfail(nullptr, AGX_E_INVALID, "agx_loop_create: struct_size %d != %zu", cfg->struct_size, sizeof(agx_loop_config));

@@ -69,6 +69,17 @@ extern "C" {
 #define AGX_OBS_F16       0x20
 #define AGX_OBS_TYPE_MASK 0x30
 
+/* colour frames: a flag bit OR-ed into agx_config.out_mode next to the AGX_OBS_* bits.  Every frame of the stack is three planes
+ * (the render's channels 0, 1, 2 in the order physics.render returns them, no luma) instead of one gray plane: the reference's
+ * declared `(frame_stack, 3, H, W)` DMC space (dmc_env.py:119-123).  Each plane goes through exactly the gray arithmetic: channel
+ * c of every output equals, bit for bit, the output of a gray context fed channel c of the same renders.  On such a context
+ *   - frames are appended by agx_ingest_rgb(.., AGX_GRAY_NONE, ..) only; agx_ingest, agx_ingest_gray_raw, the _compact forms,
+ *     agx_ingest_gray, agx_step_fixed, the packed ragged forms and agx_loop_create return AGX_E_STATE;
+ *   - agx_obs_shape reports dims[1] = 3 * frame_stack: the layout is [N][fs][3][h][w] (the same bytes as [N][3 fs][h][w]), for
+ *     agx_observe_full, agx_get_stack_u8 / agx_set_stack_u8 and the agx_fovea_* outputs alike;
+ *   - agx_algorithmic_bytes counts the three planes. */
+#define AGX_FRAME_RGB     0x100
+
 /* sensory_action_mode (fov_env.py:114-118,193-199) */
 #define AGX_MODE_ABSOLUTE 0
 #define AGX_MODE_RELATIVE 1
@@ -139,7 +150,7 @@ AGX_API int agx_destroy(agx_ctx *ctx);
 AGX_API const char *agx_last_error(const agx_ctx *ctx);
 
 /* Shape of the observation this context's kind/out_mode produces:
- * dims = {N, frame_stack, h, w}. For AGX_KIND_FLEXIBLE + AGX_OUT_RAW (ragged
+ * dims = {N, frame_stack, h, w} (AGX_FRAME_RGB: {N, 3 * frame_stack, h, w}). For AGX_KIND_FLEXIBLE + AGX_OUT_RAW (ragged
  * crops) h,w are the padded pitch obs_h,obs_w; only [0:res_h, 0:res_w] is data. */
 AGX_API int agx_obs_shape(const agx_ctx *ctx, int32_t dims[4]);
 
@@ -195,6 +206,7 @@ AGX_API int agx_profile_next(agx_ctx *ctx, int kernel_id, void *start_event, voi
  * OpenCV generation's coefficients (AGX_GRAY_*). */
 #define AGX_GRAY_CV15 0   /* OpenCV 4.x : (3735 c0 + 19235 c1 + 9798 c2 + 16384) >> 15 */
 #define AGX_GRAY_CV14 1   /* OpenCV <=3 : (1868 c0 +  9617 c1 + 4899 c2 +  8192) >> 14 */
+#define AGX_GRAY_NONE 2   /* keep the three channels, planar (AGX_FRAME_RGB contexts only; the two modes above are gray-only) */
 AGX_API int agx_ingest_rgb(agx_ctx *ctx, const uint8_t *d_frames, const uint8_t *d_cmd, int gray_mode, void *stream);
 
 /* ---- K0: base observation ----------------------------------------------
