@@ -31,16 +31,18 @@ __device__ __forceinline__ void build_taps(const PassDesc &d, Tap *tab, int tid)
     }
 }
 
-// element of a pass: src walks with `stride` floats between consecutive taps
+// element of a pass: src walks with `stride` floats between consecutive taps.  Every multiply-add is an explicit fmaf: left to
+// the compiler's contraction, the f32 / bf16 / f16 instantiations of one kernel fused a + b differently and their float32
+// values differed in the last bit, which breaks "a 16-bit observation is the float32 one rounded once".
 __device__ __forceinline__ float apply_tap(const PassDesc &d, const Tap &t, const float *src, int stride) {
-    if (!d.aa) return t.a * src[t.lo * stride] + t.b * src[t.aux * stride];
+    if (!d.aa) return fmaf(t.b, src[t.aux * stride], t.a * src[t.lo * stride]);
     float acc = 0.f;
     const float *q = src + t.lo * stride;
     for (int k = 0; k < t.aux; ++k) {
         float x = ((float)k - t.a + 0.5f) * d.inv;
         x = fabsf(x);
         const float w = x < 1.f ? 1.f - x : 0.f;
-        acc += w * q[k * stride];
+        acc = fmaf(w, q[k * stride], acc);
     }
     return acc * t.b;
 }
@@ -221,8 +223,8 @@ __global__ __launch_bounds__(kThreads) void k_fovea_generic(GeomR g, FovParams p
             const Tap t = tab[row];
             const float4 a = H4[t.lo * ow4 + x4];
             const float4 b = H4[t.aux * ow4 + x4];
-            store_obs(oout, q, make_float4(t.a * a.x + t.b * b.x, t.a * a.y + t.b * b.y,
-                                           t.a * a.z + t.b * b.z, t.a * a.w + t.b * b.w));
+            store_obs(oout, q, make_float4(fmaf(t.b, b.x, t.a * a.x), fmaf(t.b, b.y, t.a * a.y),
+                                           fmaf(t.b, b.z, t.a * a.z), fmaf(t.b, b.w, t.a * a.w)));
         }
         return;
     }

@@ -7,6 +7,8 @@
 // Usage: harness oh ow fh fw antialias          (k_fovea_flexible3 tables) -> "max_err <e> cases <n>" | "unsupported"
 //        harness per oh ow ph pw antialias      (k_fovea_peripheral3 tables + unit_fast over all 256 values)
 //        harness raw oh ow fh fw antialias      (k_fovea_flexible_raw3 tables: raw-crop / mask-out / packed forms)
+//        harness plan oh ow fh fw ph pw antialias resize|raw|mask
+//                                               which kernel form agx_create + the launch code select for each kind, and why
 #include <cstdio>
 #include <cstdlib>
 #include <random>
@@ -184,7 +186,218 @@ static int raw_main(int argc, char **argv) {
     return 0;
 }
 
+// ---- plan report: the kernel form agx_create and the launch code of agx_api.hip select for a geometry, per kind.
+// The table builders are the ones agx_create calls (agx_host_tables.h).  The predicates that live only in agx_api.hip are
+// restated here, each under the name it has there; a change to one of them there must be made here too, and the case table
+// of tests/test_geometry_plan_cpu.py is what notices a plan that moved.
+namespace plan {
+
+constexpr size_t kMaxLds = 160 * 1024;                     // agx_api.hip: kMaxLds
+
+int tap_bucket(int n) { return n <= 2 ? 2 : n <= 4 ? 4 : n <= 8 ? 8 : n <= 12 ? 12 : n <= 16 ? 16 : n; }   // agx_api.hip: tap_bucket
+
+// agx_api.hip: axis_taps - the bucketed tap bound `maxt` only (the same index arithmetic, the weights left out)
+int axis_maxt(int n_in, int n_out, bool antialias) {
+    const double scale = (double)n_in / (double)n_out;
+    const bool aa = antialias && n_in > n_out;
+    int maxt = 1;
+    for (int i = 0; i < n_out; ++i) {
+        int n;
+        if (aa) {
+            const double support = scale, center = scale * (i + 0.5);
+            long long xmin = (long long)(center - support + 0.5);
+            if (xmin < 0) xmin = 0;
+            long long xmax = (long long)(center + support + 0.5);
+            if (xmax > n_in) xmax = n_in;
+            n = xmax > xmin ? (int)(xmax - xmin) : 0;
+        } else {
+            double f = scale * (i + 0.5) - 0.5;
+            if (f < 0.0) f = 0.0;
+            int i0 = (int)f;
+            if (i0 > n_in - 1) i0 = n_in - 1;
+            n = i0 < n_in - 1 ? 2 : 1;
+        }
+        maxt = std::max(maxt, n);
+    }
+    return tap_bucket(maxt);
+}
+
+size_t per2_tables(const agx_config &c) {                  // agx_api.hip: per2_tables
+    const int m1 = axis_maxt(c.obs_h, c.per_h, c.antialias != 0), m3 = axis_maxt(c.per_h, c.obs_h, c.antialias != 0);
+    return (size_t)c.per_h * (sizeof(int2) + m1 * sizeof(float)) + (size_t)c.obs_h * (sizeof(int2) + m3 * sizeof(float));
+}
+
+size_t per2_lds(const agx_config &c) {                     // agx_api.hip: per2_lds
+    const size_t raw = ((size_t)c.obs_h * c.obs_w + 15) & ~(size_t)15;
+    const size_t ac = (std::max((size_t)c.obs_h * c.per_w, (size_t)c.per_h * c.obs_w) + 3) & ~(size_t)3;
+    const size_t b = ((size_t)c.per_h * c.per_w + 3) & ~(size_t)3;
+    return 1024 + raw + (ac + b) * sizeof(float) + per2_tables(c);
+}
+
+// agx_api.hip: build_family(...).floats[r] - LDS floats of the staged table of window size r
+size_t family_floats(int which, int r, int fov, int obs, bool antialias) {
+    const int n_in = which == 0 ? r : (which == 1 ? fov : r);
+    const int n_out = which == 0 ? fov : (which == 1 ? r : obs);
+    const int maxt = axis_maxt(n_in, n_out, antialias);
+    return (((size_t)2 * n_out + (size_t)n_out * maxt) + 3) & ~(size_t)3;
+}
+
+size_t flex_tab_floats(const agx_config &c) {              // agx_api.hip: agx_create, ctx->flex_tab_floats
+    const bool aa = c.antialias != 0;
+    size_t worst_w = 0, worst_h = 0;
+    for (int r = 1; r <= c.obs_w; ++r) {
+        size_t s = 0;
+        for (int k = 0; k < 3; ++k) s += family_floats(k, r, c.fov_w, c.obs_w, aa);
+        worst_w = std::max(worst_w, s);
+    }
+    for (int r = 1; r <= c.obs_h; ++r) {
+        size_t s = 0;
+        for (int k = 0; k < 3; ++k) s += family_floats(k, r, c.fov_h, c.obs_h, aa);
+        worst_h = std::max(worst_h, s);
+    }
+    return worst_w + worst_h;
+}
+
+size_t flex2_lds(const agx_config &c, size_t tab_floats) { // agx_api.hip: flex2_lds
+    const size_t raw = ((size_t)c.obs_h * c.obs_w + 15) & ~(size_t)15;
+    const size_t ae = (std::max((size_t)c.obs_h * c.fov_w, (size_t)c.fov_h * c.obs_w) + 3) & ~(size_t)3;
+    const size_t b = ((size_t)c.fov_h * c.fov_w + 3) & ~(size_t)3;
+    const size_t cc = ((size_t)c.fov_h * c.obs_w + 3) & ~(size_t)3;
+    return 1024 + std::max(raw, cc * sizeof(float)) + (ae + b + tab_floats) * sizeof(float);
+}
+
+size_t fixed_lds(const agx_config &c) {                    // agx_api.hip: fixed_lds
+    const size_t raw = ((size_t)c.fov_h * c.obs_w + 15) & ~(size_t)15;
+    size_t b = raw;
+    if (c.out_mode == AGX_OUT_RESIZE) b += (size_t)c.obs_h * sizeof(Tap) + (size_t)c.fov_h * c.obs_w * sizeof(float);
+    return b;
+}
+
+size_t generic_buf1(const agx_config &c) {                 // agx_api.hip: generic_buf1
+    const size_t cap = ((size_t)c.obs_h * c.obs_w + 3) & ~(size_t)3;
+    if (c.kind != AGX_KIND_PERIPHERAL) return cap;
+    const size_t abc = (size_t)c.obs_h * c.per_w + (size_t)c.per_h * c.per_w + (size_t)c.per_h * c.obs_w;
+    return (abc + 3) & ~(size_t)3;
+}
+
+size_t generic_lds(const agx_config &c) {                  // agx_api.hip: generic_lds
+    const size_t cap = ((size_t)c.obs_h * c.obs_w + 3) & ~(size_t)3;
+    int tmax = std::max(std::max(c.obs_h, c.obs_w), std::max(c.fov_h, c.fov_w));
+    if (c.kind == AGX_KIND_PERIPHERAL) tmax = std::max(tmax, std::max(c.per_h, c.per_w));
+    return (cap + generic_buf1(c)) * sizeof(float) + (size_t)tmax * sizeof(Tap);
+}
+
+// agx_api.hip: agx_create, "the LDS of the kernel that will actually run" (no knob set).  0 = accepted, else the bytes in
+// the message "geometry needs %zu B of LDS per workgroup (limit %zu)"
+size_t create_refusal(const agx_config &c) {
+    const bool per_tuned = per2_lds(c) <= kMaxLds && c.per_w <= kThreads;
+    const size_t lds = c.kind == AGX_KIND_FIXED ? fixed_lds(c)
+                       : (c.kind == AGX_KIND_PERIPHERAL && per_tuned ? per2_lds(c) : generic_lds(c));
+    return lds > kMaxLds ? lds : 0;
+}
+
+void print_set(const char *key, const std::vector<int2> &meta, int from, int to) {
+    bool has[17] = {};
+    for (int r = from; r <= to; ++r) has[meta[r].x] = true;
+    printf(" %s=", key);
+    bool any = false;
+    for (int t : {4, 8, 16})
+        if (has[t]) { printf("%s%d", any ? "," : "", t); any = true; }
+    if (!any) printf("-");
+}
+
+// why a composed-operator plan (build_flex3 / build_flexraw) does not apply: their entry guards restated, everything
+// behind the guards is a tap bound (a bucket overflows, or an up-scale row has more taps than the kernel's 2 or 3)
+const char *composed_refusal(const agx_config &c, bool ok, size_t lds) {
+    if (c.obs_w > kThreads) return "obs_w>256";
+    if (c.fov_h > kThreads / 8) return "fov_h>32";
+    if (c.obs_h > 1024) return "obs_h>1024";
+    if (!ok) return "taps";
+    if (lds > kMaxLds) return "lds";
+    return nullptr;
+}
+
+// agx_fovea_flexible / agx_fovea_flexible_packed behind a refused composed plan
+const char *flex_fallback(const agx_config &c, size_t *lds) {
+    const size_t lds2 = flex2_lds(c, flex_tab_floats(c));
+    if (lds2 <= kMaxLds) { *lds = lds2; return "flexible2"; }
+    *lds = generic_lds(c);
+    return "generic";
+}
+
+int run(int argc, char **argv) {
+    if (argc < 10) return 2;
+    agx_config c{};
+    c.obs_h = atoi(argv[2]); c.obs_w = atoi(argv[3]); c.fov_h = atoi(argv[4]); c.fov_w = atoi(argv[5]);
+    c.per_h = atoi(argv[6]); c.per_w = atoi(argv[7]); c.antialias = atoi(argv[8]);
+    const char *mode = argv[9];
+    const int out_mode = !strcmp(mode, "resize") ? AGX_OUT_RESIZE : !strcmp(mode, "mask") ? AGX_OUT_MASK : !strcmp(mode, "raw") ? AGX_OUT_RAW : -1;
+    if (out_mode < 0) return 2;
+    const bool headline = c.obs_h == 84 && c.obs_w == 84 && c.fov_h == 30 && c.fov_w == 30;
+    size_t refused;
+    // ---- fixed (agx_fovea_fixed)
+    c.kind = AGX_KIND_FIXED;
+    c.out_mode = out_mode;
+    if ((refused = create_refusal(c))) printf("fixed form=refused lds=%zu\n", refused);
+    else printf("fixed form=%s lds=%zu\n", headline ? "fixed<GeomS>" : "fixed<GeomR>", fixed_lds(c));
+    // ---- flexible (agx_fovea_flexible, agx_fovea_flexible_packed)
+    c.kind = AGX_KIND_FLEXIBLE;
+    if ((refused = create_refusal(c))) printf("flexible form=refused lds=%zu\n", refused);
+    else if (out_mode == AGX_OUT_RESIZE) {
+        const Flex3Host h = build_flex3(c);
+        const size_t lds3 = h.ok ? flex3_lds(h, c) : 0;
+        const char *why = composed_refusal(c, h.ok, lds3);
+        if (!why) {
+            printf("flexible form=flex3");
+            print_set("W", h.wc_meta, 1, c.obs_w);
+            print_set("H", h.hd_meta, c.fov_h + 1, c.obs_h);
+            printf(" rstep=%d lds=%zu\n", kThreads / c.obs_w, lds3);
+        } else {
+            size_t lds = 0;
+            const char *form = flex_fallback(c, &lds);
+            printf("flexible form=%s why=%s lds=%zu\n", form, why, lds);
+        }
+    } else {
+        const FlexRawHost h = build_flexraw(c);
+        const size_t ldsr = h.ok ? h.lds(c) : 0;
+        const char *why = composed_refusal(c, h.ok, ldsr);
+        if (!why) {
+            printf("flexible form=raw3");
+            print_set("W", h.wb_meta, 1, c.obs_w);
+            print_set("H", h.hd_meta, c.fov_h + 1, c.obs_h);
+            printf(" rstep=%d lds=%zu packed=raw3\n", kThreads / c.obs_w, ldsr);
+        } else {
+            size_t lds = 0;
+            const char *form = flex_fallback(c, &lds);
+            printf("flexible form=%s why=%s lds=%zu packed=offsets+%s\n", form, why, lds, form);
+        }
+    }
+    // ---- peripheral (agx_fovea_peripheral): always resize_to_full (pipeline.py, fov_env.py:361-364)
+    c.kind = AGX_KIND_PERIPHERAL;
+    c.out_mode = AGX_OUT_RESIZE;
+    if (c.per_h < 1 || c.per_w < 1) printf("peripheral form=none\n");
+    else if ((refused = create_refusal(c))) printf("peripheral form=refused lds=%zu\n", refused);
+    else {
+        const Per3Host h = build_per3(c);
+        const int same = (c.per_h == c.obs_h && c.per_w == c.obs_w) ? 1 : 0;
+        if (h.ok && h.lds <= kMaxLds) printf("peripheral form=per3 mt=%d same=%d lds=%zu\n", h.mt, same, h.lds);
+        else {
+            const char *why = h.ok ? "lds" : (c.obs_w > kThreads ? "obs_w>256" : c.per_w > kThreads ? "per_w>256" : c.per_h > 256 ? "per_h>256" : "taps");
+            if (per2_lds(c) <= kMaxLds && c.per_w <= kThreads) {
+                const bool aa = c.antialias != 0;
+                const int m0 = axis_maxt(c.obs_w, c.per_w, aa), m1 = axis_maxt(c.obs_h, c.per_h, aa);
+                printf("peripheral form=peripheral2 mt=%d same=%d why=%s lds=%zu\n", m0 == m1 && m0 <= 16 ? m0 : 0, same, why, per2_lds(c));
+            } else
+                printf("peripheral form=generic same=%d why=%s lds=%zu\n", same, why, generic_lds(c));
+        }
+    }
+    return 0;
+}
+
+}  // namespace plan
+
 int main(int argc, char **argv) {
+    if (argc > 1 && !strcmp(argv[1], "plan")) return plan::run(argc, argv);
     if (argc > 1 && !strcmp(argv[1], "per")) return per_main(argc, argv);
     if (argc > 1 && !strcmp(argv[1], "raw")) return raw_main(argc, argv);
     if (argc < 6) return 2;

@@ -1,10 +1,15 @@
 """Randomised-geometry parity fuzz on the GPU: random obs / fov / peripheral sizes, frame stacks, modes, antialias and
 actions (incl. out-of-range and .5 ties) through libagx against the oracle, for a time budget.  Exits non-zero on the
-first mismatch and prints the configuration that produced it.
+first mismatch and prints the configuration that produced it, with the kernel forms its geometry selects.
 
     python tools/fuzz_gpu.py [seconds] [seed]
+    python tools/fuzz_gpu.py --case K [seed]       # case K of that seed alone (every case draws from its own stream)
+
+The kernel forms come from `host_tables_harness plan` (tests/host_tables_harness.cpp) where that program has been built as
+tools/host_tables_harness (or AGX_HARNESS names it):
+    hipcc -O1 -std=c++17 -x hip --offload-arch=gfx950 -I include -I active-gym_amd/csrc tests/host_tables_harness.cpp -o tools/host_tables_harness
 """
-import os, sys, time, traceback
+import os, subprocess, sys, time, traceback
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [os.path.join(REPO, "active-gym_amd"), REPO]
 import numpy as np
@@ -13,9 +18,15 @@ from active_gym import ObsPipeline
 from active_gym._native import AgxError
 from oracle import oracle as O
 
-budget = float(sys.argv[1]) if len(sys.argv) > 1 else 120.0
-seed = int(sys.argv[2]) if len(sys.argv) > 2 else 0
-rng = np.random.default_rng(seed)
+argv = sys.argv[1:]
+only = None
+if argv and argv[0] == "--case":
+    only, argv = int(argv[1]), [None] + argv[2:]
+budget = float(argv[0]) if argv and argv[0] is not None else 120.0
+seed = int(argv[1]) if len(argv) > 1 else 0
+rng = None                                                   # one_case(k) draws from a stream of its own: (seed, k)
+HARNESS = os.environ.get("AGX_HARNESS", os.path.join(REPO, "tools", "host_tables_harness"))
+last_cfg = {}
 dev = torch.device("cuda:0")
 TOL = 1e-5
 
@@ -28,7 +39,23 @@ def t(x):
     return torch.from_numpy(np.ascontiguousarray(x)).to(dev)
 
 
+def plan_label(cfg):
+    """The kernel forms the geometry of `cfg` selects, from the CPU harness; a note where that has not been built."""
+    if "fov" not in cfg:
+        return "(ingest case: no fovea kernel)"
+    if not os.path.exists(HARNESS):
+        return f"(no plan: {HARNESS} is not built)"
+    per = cfg.get("per", (1, 1))
+    r = subprocess.run([HARNESS, "plan", *map(str, (*cfg["obs"], *cfg["fov"], *per, int(cfg["aa"]), cfg["out"]))],
+                       capture_output=True, text=True)
+    want = {"fixed": "fixed", "flexible": "flexible", "peripheral": "peripheral"}[cfg["kind"]]
+    return "; ".join(ln for ln in r.stdout.splitlines() if ln.startswith(want + " ")) or r.stdout + r.stderr
+
+
 def one_case(k):
+    global rng
+    rng = np.random.default_rng((seed, k))
+    last_cfg.clear()
     kind = ["fixed", "flexible", "peripheral", "ingest", "ingest_gray", "ingest_rgb"][k % 6]
     oh = int(rng.integers(3, 33)) * 4
     ow = oh if kind in ("ingest", "ingest_gray") or rng.random() < 0.5 else int(rng.integers(3, 33)) * 4
@@ -90,9 +117,12 @@ def one_case(k):
     kw = dict(obs_size=(oh, ow), fov_size=(fh, fw), fov_init_loc=init, sensory_action_mode=mode,
               sensory_action_space=(-7.0, 9.0), antialias=aa)
     cfg.update(fov=(fh, fw), mode=mode, out=out, aa=aa, init=init)
+    last_cfg.update(cfg)
     if kind == "peripheral":
         per = (int(rng.integers(1, oh + 1)), int(rng.integers(1, ow + 1)))
         cfg["per"] = per
+        cfg["out"] = "resize"
+        last_cfg.update(cfg)
         okw = dict(peripheral_res=per, **kw)
         pkw = dict(peripheral_res=per, resize_to_full=True, **kw)
         orc = lambda: O.PeripheralOracle(**okw)
@@ -166,13 +196,19 @@ t0 = time.time()
 n = rejected = 0
 kinds = {}
 reasons = {}
+if only is not None:
+    n, budget = only, float("inf")
 while time.time() - t0 < budget:
     try:
         c = one_case(n)
     except Exception:                                        # noqa: BLE001 - report and stop
         traceback.print_exc()
-        print("FUZZ FAILURE after", n, "cases, seed", seed, flush=True)
+        print("FUZZ FAILURE in case", n, "of seed", seed, "- re-run it alone with: --case", n, seed, flush=True)
+        print("plan:", plan_label(last_cfg), flush=True)
         sys.exit(1)
+    if only is not None:
+        print("case", n, "of seed", seed, "ok:", c, "\nplan:", plan_label(last_cfg or c))
+        sys.exit(0)
     n += 1
     rejected += "rejected" in c
     if "rejected" in c:
