@@ -36,12 +36,11 @@ struct agx_ctx {
     int4 *in_ytab = nullptr;
     int2 *in_xtab12 = nullptr; // K1 band12 form: {2 * x0, (a0 | a1 << 16) << 4} / {b0 << 8, b1 << 8}
     int2 *in_ytab12 = nullptr;
-    bool band12_ok = false;    // 12-row bands all full, affine source rows, every x tap pair adjacent
+    K1Plan k1;                 // what build_k1 derives from obs_size: affine row form, band12_ok / compact12_ok, band_rows
     // compact source screens (agx_ingest_compact): the source rows the vertical resize reads, ascending, and the y table with
-    // PACKED row indices; compact12_ok: band12_ok and every (y0, y1) pair disjoint and ascending (packed rows 2 dy, 2 dy + 1)
+    // PACKED row indices
     std::vector<int32_t> src_rows;
     int4 *in_ytab_c = nullptr;
-    bool compact12_ok = false;
     Tap *fx_xtab = nullptr;    // K2 tables
     Tap *fx_ytab = nullptr;
     int2 *per_ln[4] = {nullptr, nullptr, nullptr, nullptr};   // K3 tables
@@ -71,10 +70,8 @@ struct agx_ctx {
     hipStream_t aux[3] = {nullptr, nullptr, nullptr};
     hipEvent_t ev_fork = nullptr, ev_join[3] = {nullptr, nullptr, nullptr};
 #endif
-    int band_rows = 0;
+    int band_rows = 0;         // rows per band of the RGB whole-screen ingest: k1.band_rows unless an experiments knob is set
     int ingest_t = 256;
-    int rows_touched = 0;
-    int y_affine = 0, y_mul = 0, y_add = 0, y_shift = 0;   // see IngestParams
     int init_r = 0, init_c = 0;
     hipEvent_t prof[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};   // agx_profile_next: [ingest | fovea][start | stop]
     // Testing knobs, read from the environment ONCE PER CONTEXT in agx_create (so one process can hold contexts of
@@ -153,34 +150,6 @@ struct HipDeviceApi {
 using DeviceGuard = agx::DeviceGuardT<HipDeviceApi>;      // agx_device_guard.h (unit-tested with a mocked runtime)
 
 inline hipStream_t S(void *s) { return static_cast<hipStream_t>(s); }
-
-// ---- OpenCV 8-bit INTER_LINEAR tables (imgproc/src/resize.cpp), see oracle/oracle.py for the
-// restated algorithm: inv_scale = dst/src, scale = 1/inv_scale, f = (float)((d+.5)*scale-.5),
-// s = floor(f), f -= s, coefficients = rint-half-even(float * 2048).
-inline int cv_round_f(float v) { return (int)std::nearbyintf(v); }   // default mode: half-to-even
-
-void cv_axis(int src, int dst, bool is_x, std::vector<int> &i0, std::vector<int> &i1,
-             std::vector<int> &c0, std::vector<int> &c1) {
-    const double inv_scale = (double)dst / (double)src;
-    const double scale = 1.0 / inv_scale;
-    i0.resize(dst); i1.resize(dst); c0.resize(dst); c1.resize(dst);
-    for (int d = 0; d < dst; ++d) {
-        float f = (float)((d + 0.5) * scale - 0.5);
-        int s = (int)std::floor(f);
-        f -= (float)s;
-        if (is_x) {                       // x axis: clamp index and zero the fraction
-            if (s < 0) { s = 0; f = 0.f; }
-            if (s >= src - 1) { s = src - 1; f = 0.f; }
-            i0[d] = s;
-            i1[d] = std::min(s + 1, src - 1);
-        } else {                          // y axis: keep coefficients, clip the row indices
-            i0[d] = std::min(std::max(s, 0), src - 1);
-            i1[d] = std::min(std::max(s + 1, 0), src - 1);
-        }
-        c0[d] = cv_round_f((1.f - f) * 2048.f);
-        c1[d] = cv_round_f(f * 2048.f);
-    }
-}
 
 // One axis of torchvision Resize (ATen upsample_bilinear2d, align_corners=False) as explicit taps:
 // antialiased triangle filter when down-scaling with antialias on (_compute_indices_min_size_weights_aa),
@@ -508,78 +477,35 @@ int agx_create(const agx_config *cfg, agx_ctx **out) {
         TRY(hipMalloc(reinterpret_cast<void **>(&ctx->head[b]), N * sizeof(int32_t)));
         TRY(hipMemset(ctx->head[b], 0, N * sizeof(int32_t)));
     }
-    // K1 tables (only meaningful for square obs; built anyway, agx_ingest checks)
+    // K1 tables and plan (only meaningful for square obs; built anyway, agx_ingest checks): build_k1, agx_host_tables.h
     {
-        std::vector<int> x0, x1, a0, a1, y0, y1, b0, b1;
-        cv_axis(kRawW, c.obs_w, true, x0, x1, a0, a1);
-        cv_axis(kRawH, c.obs_h, false, y0, y1, b0, b1);
-        std::vector<int2> xt(c.obs_w);
-        std::vector<int4> yt(c.obs_h);
-        for (int i = 0; i < c.obs_w; ++i) xt[i] = make_int2(x0[i] | (x1[i] << 16), (a0[i] & 0xFFFF) | (a1[i] << 16));
-        std::set<int> touched;
-        for (int i = 0; i < c.obs_h; ++i) {
-            yt[i] = make_int4(y0[i], y1[i], b0[i], b1[i]);
-            touched.insert(y0[i]);
-            touched.insert(y1[i]);
+        const K1Host k1 = build_k1(c.obs_h, c.obs_w);
+        ctx->k1 = k1.plan;
+        ctx->src_rows = k1.src_rows;
+        std::vector<int2> xt(c.obs_w), xt12(c.obs_w), yt12(c.obs_h);
+        std::vector<int4> yt(c.obs_h), ytc(c.obs_h);
+        for (int i = 0; i < c.obs_w; ++i) {
+            xt[i] = make_int2(k1.x0[i] | (k1.x1[i] << 16), (k1.a0[i] & 0xFFFF) | (k1.a1[i] << 16));
+            // band12 form: the same coefficients in the shape its phase 2 consumes
+            xt12[i] = make_int2(2 * k1.x0[i], (int)((((uint32_t)k1.a0[i] & 0xFFFFu) | ((uint32_t)k1.a1[i] << 16)) << 4));
         }
-        ctx->rows_touched = (int)touched.size();
-        // compact screens: packed index of every touched source row, the y table in packed indices
-        ctx->src_rows.assign(touched.begin(), touched.end());
-        std::vector<int> packed_of(kRawH, -1);
-        for (size_t k = 0; k < ctx->src_rows.size(); ++k) packed_of[ctx->src_rows[k]] = (int)k;
-        std::vector<int4> ytc(c.obs_h);
-        bool pairs = true;
         for (int i = 0; i < c.obs_h; ++i) {
-            ytc[i] = make_int4(packed_of[y0[i]], packed_of[y1[i]], b0[i], b1[i]);
-            pairs = pairs && ytc[i].x == 2 * i && ytc[i].y == 2 * i + 1;
+            yt[i] = make_int4(k1.y0[i], k1.y1[i], k1.b0[i], k1.b1[i]);
+            ytc[i] = make_int4(k1.py0[i], k1.py1[i], k1.b0[i], k1.b1[i]);
+            yt12[i] = make_int2(k1.b0[i] << 8, k1.b1[i] << 8);
         }
         if ((rc = upload(ctx, &ctx->in_ytab_c, ytc)) != AGX_OK) return bail(rc);
-        // look for an exact integer form of the row table: y0 = (dy*mul + add) >> shift, y1 = min(y0+1, H-1)
-        for (int sh = 0; sh <= 12 && !ctx->y_affine; ++sh) {
-            const long mul = std::lround((double)kRawH / c.obs_h * (double)(1 << sh));
-            for (long add = -(1L << sh); add <= (1L << (sh + 1)) && !ctx->y_affine; ++add) {
-                bool ok = true;
-                for (int i = 0; i < c.obs_h && ok; ++i) {
-                    const long v = (i * mul + add) >> sh;
-                    ok = v >= 0 && v == y0[i] && std::min<long>(v + 1, kRawH - 1) == y1[i];
-                }
-                if (ok) {
-                    ctx->y_affine = 1;
-                    ctx->y_mul = (int)mul;
-                    ctx->y_add = (int)add;
-                    ctx->y_shift = sh;
-                }
-            }
-        }
         if ((rc = upload(ctx, &ctx->in_xtab, xt)) != AGX_OK) return bail(rc);
         if ((rc = upload(ctx, &ctx->in_ytab, yt)) != AGX_OK) return bail(rc);
-        // band12 form: the same coefficients in the shape its phase 2 consumes
-        std::vector<int2> xt12(c.obs_w), yt12(c.obs_h);
-        bool adjacent = true;
-        for (int i = 0; i < c.obs_w; ++i) {
-            adjacent = adjacent && x1[i] == x0[i] + 1;
-            xt12[i] = make_int2(2 * x0[i], (int)((((uint32_t)a0[i] & 0xFFFFu) | ((uint32_t)a1[i] << 16)) << 4));
-        }
-        for (int i = 0; i < c.obs_h; ++i) yt12[i] = make_int2(b0[i] << 8, b1[i] << 8);
         if ((rc = upload(ctx, &ctx->in_xtab12, xt12)) != AGX_OK) return bail(rc);
         if ((rc = upload(ctx, &ctx->in_ytab12, yt12)) != AGX_OK) return bail(rc);
-        ctx->band12_ok = adjacent && ctx->y_affine && c.obs_h % 12 == 0 && (c.obs_w / 4) * 12 <= kThreads;
-        // phase 2 of the band12 form reads 8 bytes at byte (2 x0) & ~3 of a 320-byte gray row: never past the row + the slack above
-        for (int i = 0; i < c.obs_w && ctx->band12_ok; ++i)
-            if (((2 * x0[i]) & ~3) + 8 > 2 * kRawW + 8) ctx->band12_ok = false;
-        ctx->compact12_ok = ctx->band12_ok && pairs;
-        // ingest workgroup: T threads produce band_rows output rows (band_rows * ow/4 <= T and the
-        // 2 * band_rows row jobs fit the T/40 loader groups x 4 iterations).  128-thread workgroups give
-        // 16 independent workgroups per CU whose load / compute phases interleave (AGX_INGEST_T tunes).
-        const int ow4 = c.obs_w / 4;
+        // the RGB whole-screen ingest: 128-thread workgroups give 16 independent workgroups per CU whose load / compute
+        // phases interleave (AGX_INGEST_T tunes; 8 WGs/CU whatever T: 256 fills the wave slots), fewer rows per band
+        // (AGX_INGEST_BAND_ROWS).  Both knobs are 0 in the shipped library: band_rows is then the plan's.
         const int forced_t = ctx->tune.ingest_t;
-        ctx->ingest_t = (forced_t == 128 || forced_t == 256) ? forced_t : 256;   // 8 WGs/CU whatever T: 256 fills the wave slots
-        if (ow4 > 128) ctx->ingest_t = 256;
-        ctx->band_rows = std::max(1, std::min(2 * (ctx->ingest_t / 40), ctx->ingest_t / ow4));
-        // tuning knob (bands per env).  Measured at N=1024, same box: 12 rows x 7 bands (3.5 rounds of 2048 resident
-        // workgroups) 46.0-46.7 us; 11 x 8 (4.0 rounds) 50-52; 10 x 9 53; and with wider workgroups whose grids are
-        // exact rounds - 320 thr x 14 rows, 384 x 18, 512 x 21 - 50.2 / 49.2 / 48.5 us: the half-empty last round is
-        // not what limits this kernel.
+        ctx->ingest_t = (forced_t == 128 || forced_t == 256) ? forced_t : 256;
+        if (c.obs_w / 4 > 128) ctx->ingest_t = 256;
+        ctx->band_rows = k1_band_rows(c.obs_w, ctx->ingest_t);
         const int forced_br = ctx->tune.band_rows;
         if (forced_br >= 1 && forced_br <= ctx->band_rows) ctx->band_rows = forced_br;
     }
@@ -732,9 +658,9 @@ int64_t agx_algorithmic_bytes(const agx_ctx *ctx, int kernel_id) {
         return AGX_E_STATE;   // the raw-screen ingests do not run on a colour context
     switch (kernel_id) {
         case AGX_K_INGEST:   // two frames, only the source rows the vertical resize touches + one u8 slot
-            return N * (2 * (int64_t)ctx->rows_touched * kRawRowBytes + px);
+            return N * (2 * (int64_t)ctx->k1.rows_touched * kRawRowBytes + px);
         case AGX_K_INGEST_GRAY_RAW:   // two gray frames, only the touched source rows, + one u8 slot
-            return N * (2 * (int64_t)ctx->rows_touched * kRawW + px);
+            return N * (2 * (int64_t)ctx->k1.rows_touched * kRawW + px);
         case AGX_K_INGEST_RGB:   // one obs-sized RGB render in, one u8 slot out (colour: three u8 planes out)
             return N * px * (3 + ctx->planes);
         case AGX_K_FULL:
@@ -773,10 +699,10 @@ static IngestParams ingest_params(agx_ctx *ctx, const uint8_t *d_frames, const u
     p.ow = c.obs_w;
     p.fs = c.frame_stack;
     p.band_rows = ctx->band_rows;
-    p.y_affine = ctx->y_affine;
-    p.y_mul = ctx->y_mul;
-    p.y_add = ctx->y_add;
-    p.y_shift = ctx->y_shift;
+    p.y_affine = ctx->k1.y_affine;
+    p.y_mul = ctx->k1.y_mul;
+    p.y_add = ctx->k1.y_add;
+    p.y_shift = ctx->k1.y_shift;
     p.nbands = (c.obs_h + ctx->band_rows - 1) / ctx->band_rows;
     p.xtab12 = ctx->in_xtab12;
     p.ytab12 = ctx->in_ytab12;
@@ -787,6 +713,12 @@ static IngestParams ingest_params(agx_ctx *ctx, const uint8_t *d_frames, const u
     if (const char *e = getenv("AGX_DBG_PTR")) p.stamps = reinterpret_cast<unsigned long long *>(strtoull(e, nullptr, 0));
 #endif
     return p;
+}
+
+// agx_ingest_gray_raw: the plan's 256-thread bands (AGX_INGEST_BAND_ROWS of the experiments build narrows them as it does the
+// RGB ingest's; the other opt-in variants are RGB-only)
+static int gray_band_rows(const agx_ctx *ctx) {
+    return ctx->ingest_t == 256 ? std::min(ctx->k1.band_rows, ctx->band_rows) : ctx->k1.band_rows;
 }
 
 static size_t ingest_lds(const agx_ctx *ctx) {
@@ -818,7 +750,7 @@ int agx_ingest(agx_ctx *ctx, const uint8_t *d_frames, const uint8_t *d_cmd, void
     // (measured equal to the barrier form at N=1024 - 46.5 vs 45.6 us - so it is opt-in: AGX_INGEST_WAVE=1)
     const bool want_wave = ctx->tune.wave != 0;
     const int rpw = ctx->band_rows / 4;
-    const bool wave_ok = want_wave && pipe_parts == 0 && ctx->ingest_t == 256 && ctx->y_affine && ctx->band_rows % 4 == 0 &&
+    const bool wave_ok = want_wave && pipe_parts == 0 && ctx->ingest_t == 256 && ctx->k1.y_affine && ctx->band_rows % 4 == 0 &&
                          rpw >= 1 && rpw <= 3 && rpw * (c.obs_w / 4) <= 64;
     if (wave_ok) {
         const size_t slice = ((sizeof(int2) * c.obs_w + (size_t)2 * rpw * kRawW * 2) + 15) & ~(size_t)15;
@@ -832,7 +764,7 @@ int agx_ingest(agx_ctx *ctx, const uint8_t *d_frames, const uint8_t *d_cmd, void
     // (same box, N=1024: 37.5-37.9 us against 37.9-38.2 for the one-band form - K1 is VALU-issue- and HBM-limited, not
     //  limited by the load-free tail of a workgroup - so it stays opt-in)
     else if (ctx->tune.no_full == 0 && ctx->tune.pair12 != 0 && ctx->tune.band_rows == 0 && ctx->tune.ingest_t == 0 &&
-             ctx->y_affine && ctx->band_rows == 12 && c.obs_h % 12 == 0 && (c.obs_w / 4) * 12 <= kThreads)
+             ctx->k1.y_affine && ctx->band_rows == 12 && c.obs_h % 12 == 0 && (c.obs_w / 4) * 12 <= kThreads)
         AGX_LAUNCH(0, k_ingest_pair12, dim3(bands, (c.num_envs + 1) / 2), dim3(256), lds + (size_t)2 * 12 * 2 * kRawW, S(stream), p,
                    (int)c.num_envs);
     else launched = false;
@@ -841,7 +773,7 @@ int agx_ingest(agx_ctx *ctx, const uint8_t *d_frames, const uint8_t *d_cmd, void
     {
         // the headline form where its plan applies (12-row bands all full, affine source rows, adjacent x taps), the general
         // band kernel otherwise
-        if (ctx->tune.no_full == 0 && ctx->band12_ok && ctx->band_rows == 12)
+        if (ctx->tune.no_full == 0 && k1_band12(ctx->k1, false, ctx->band_rows))
             AGX_LAUNCH(0, k_ingest_full12, dim3(bands, c.num_envs), dim3(256), band12_lds(ctx), S(stream), p);
         else
             AGX_LAUNCH(0, k_ingest<256>, dim3(bands, c.num_envs), dim3(256), lds, S(stream), p);
@@ -860,12 +792,10 @@ int agx_ingest_gray_raw(agx_ctx *ctx, const uint8_t *d_gray, const uint8_t *d_cm
         return fail(ctx, AGX_E_STATE, "agx_ingest_gray_raw needs a square obs_size (cv2.resize takes (width, height): atari_env.py:74)");
     DeviceGuard g(c.device);
     IngestParams p = ingest_params(ctx, d_gray, d_cmd);
-    // always the default 256-thread band form (the opt-in variants are RGB-only)
-    const int br = std::max(1, std::min(2 * (kThreads / 40), kThreads / (c.obs_w / 4)));
-    p.band_rows = std::min(br, ctx->band_rows > 0 && ctx->ingest_t == 256 ? ctx->band_rows : br);
+    p.band_rows = gray_band_rows(ctx);
     p.nbands = (c.obs_h + p.band_rows - 1) / p.band_rows;
     const size_t lds = sizeof(int4) * p.band_rows + sizeof(int2) * c.obs_w + (size_t)2 * p.band_rows * 2 * kRawW;
-    if (ctx->tune.no_full == 0 && ctx->band12_ok && p.band_rows == 12)
+    if (ctx->tune.no_full == 0 && k1_band12(ctx->k1, false, p.band_rows))
         AGX_LAUNCH(0, k_ingest_grayraw_full12, dim3(p.nbands, c.num_envs), dim3(kThreads), band12_lds(ctx), S(stream), p);
     else
         AGX_LAUNCH(0, k_ingest_grayraw, dim3(p.nbands, c.num_envs), dim3(kThreads), lds, S(stream), p);
@@ -895,12 +825,12 @@ static int ingest_compact(agx_ctx *ctx, const uint8_t *d_rows, const uint8_t *d_
     p.src_rows = (int32_t)ctx->src_rows.size();
     p.ytab = ctx->in_ytab_c;             // packed row indices
     p.y_affine = 0;
-    const int br = std::max(1, std::min(2 * (kThreads / 40), kThreads / (c.obs_w / 4)));
+    const int br = ctx->k1.band_rows;    // always the default 256-thread band form
     p.band_rows = br;
     p.nbands = (c.obs_h + br - 1) / br;
     const size_t lds = sizeof(int4) * br + sizeof(int2) * c.obs_w + (size_t)2 * br * 2 * kRawW;
     const dim3 grid(p.nbands, c.num_envs), block(kThreads);
-    if (ctx->tune.no_full == 0 && ctx->compact12_ok && br == 12) {
+    if (ctx->tune.no_full == 0 && k1_band12(ctx->k1, true, br)) {
         if (gray) AGX_LAUNCH(0, k_ingest_grayraw_full12_compact, grid, block, band12_lds(ctx), S(stream), p);
         else AGX_LAUNCH(0, k_ingest_full12_compact, grid, block, band12_lds(ctx), S(stream), p);
     } else {
@@ -1206,7 +1136,7 @@ int agx_step_fixed(agx_ctx *ctx, const uint8_t *d_frames, const uint8_t *d_cmd, 
     parts = std::min(std::min(parts, 4), c.num_envs);
     // ---- one launch, one workgroup per env (agx_step_env.h): the headline geometry's resize_to_full path
     if (tn.step_env != 0 && default_forms && !mid_event && c.out_mode == AGX_OUT_RESIZE && c.obs_h == 84 && c.obs_w == 84 &&
-        c.fov_h == 30 && c.fov_w == 30 && ctx->y_affine && ctx->band_rows == 12 && c.frame_stack >= 1) {
+        c.fov_h == 30 && c.fov_w == 30 && ctx->k1.y_affine && ctx->band_rows == 12 && c.frame_stack >= 1) {
         DeviceGuard g(c.device);
         const IngestParams pi = ingest_params(ctx, d_frames, d_cmd);
         FovParams pf = fov_params(ctx, d_action, action_dtype, nullptr, nullptr, d_obs, d_fov_loc, nullptr);
@@ -1245,7 +1175,7 @@ int agx_step_fixed(agx_ctx *ctx, const uint8_t *d_frames, const uint8_t *d_cmd, 
         const bool crop = c.out_mode == AGX_OUT_RAW;
         const size_t obs_env = (size_t)c.frame_stack * (crop ? (size_t)c.fov_h * c.fov_w : fsz);
         const bool wide = action_dtype == AGX_DT_F64 || action_dtype == AGX_DT_I64;
-        const bool full12 = ctx->y_affine && ctx->band_rows == 12 && c.obs_h % 12 == 0;
+        const bool full12 = ctx->k1.y_affine && ctx->band_rows == 12 && c.obs_h % 12 == 0;
         const bool headline = c.obs_h == 84 && c.obs_w == 84 && c.fov_h == 30 && c.fov_w == 30;
         using GS = GeomS<84, 84, 30, 30>;
         const GeomR gr{c.obs_h, c.obs_w, c.fov_h, c.fov_w};
@@ -1308,7 +1238,7 @@ int agx_step_fixed(agx_ctx *ctx, const uint8_t *d_frames, const uint8_t *d_cmd, 
         pf.cmd = d_cmd;
         pf.phase = 1;
         pf.head = ctx->head[ctx->cur_head];                  // the head BEFORE this step's ingest
-        const bool b12 = ctx->tune.fused >= 2 && ctx->band12_ok && ctx->band_rows == 12;      // AGX_STEP_FUSED=2 / 3: band12 ingest body
+        const bool b12 = ctx->tune.fused >= 2 && ctx->k1.band12_ok && ctx->band_rows == 12;      // AGX_STEP_FUSED=2 / 3: band12 ingest body
         const size_t lds = std::max(b12 ? band12_lds(ctx) : ingest_lds(ctx), fixed_lds(c));
         const dim3 grid1(pi.nbands + c.frame_stack, c.num_envs), grid2(1, c.num_envs), block(kThreads);
         using GS = GeomS<84, 84, 30, 30>;
@@ -1585,11 +1515,7 @@ int agx_step_flexible_packed(agx_ctx *ctx, const uint8_t *d_screens, int screens
     const bool gray = (screens & AGX_SCREENS_GRAY) != 0, compact = (screens & AGX_SCREENS_COMPACT) != 0;
     // the two-launch form needs the band12 ingest plan for this layout and the raw3 crop plan; everything else (and
     // AGX_STEP_PACKED_UNFUSED=1, for A/B runs) is the three launches of the stand-alone entry points, same results
-    const int br_def = std::max(1, std::min(2 * (kThreads / 40), kThreads / std::max(1, c.obs_w / 4)));
-    bool band12;
-    if (compact) band12 = ctx->compact12_ok && br_def == 12;
-    else if (gray) band12 = ctx->band12_ok && std::min(br_def, ctx->band_rows > 0 && ctx->ingest_t == 256 ? ctx->band_rows : br_def) == 12;
-    else band12 = ctx->band12_ok && ctx->band_rows == 12;
+    const bool band12 = k1_band12(ctx->k1, compact, compact ? ctx->k1.band_rows : (gray ? gray_band_rows(ctx) : ctx->band_rows));
     const int nb = (c.num_envs + kScanEnvsPerBlock - 1) / kScanEnvsPerBlock;
     const bool fused = c.obs_h == c.obs_w && band12 && ctx->tune.no_full == 0 && packed_raw3_ok(ctx) && c.num_envs + nb <= 65535 &&
                        ctx->tune.packed_unfused == 0 && ctx->tune.packed_wave == 0 &&

@@ -1,8 +1,12 @@
 // agx_host_tables.h - HOST side: the per-context operator tables of the composed-operator kernels
-// (k_fovea_flexible3, agx_k4_flex3.h), built from agx_rows.h.  Included by agx_api.hip and by the CPU test
-// harness tests/host_tables_harness.cpp, which replays the kernels' arithmetic from these very tables.
+// (k_fovea_flexible3, agx_k4_flex3.h), built from agx_rows.h, and the K1 ingest tables with the plan agx_create derives
+// from them (build_k1).  Included by agx_api.hip and by the CPU test harness tests/host_tables_harness.cpp, which replays
+// the kernels' arithmetic from these very tables and reports the plans.
 #pragma once
+#include <algorithm>
+#include <cmath>
 #include <cstring>
+#include <set>
 #include <vector>
 
 #include "agx.h"
@@ -13,6 +17,120 @@
 #include "agx_rows.h"
 
 namespace agx {
+
+// ---- K1 ingest (agx_k1_ingest.h): OpenCV 8-bit INTER_LINEAR tables (imgproc/src/resize.cpp), see oracle/oracle.py for
+// the restated algorithm: inv_scale = dst/src, scale = 1/inv_scale, f = (float)((d+.5)*scale-.5),
+// s = floor(f), f -= s, coefficients = rint-half-even(float * 2048).
+inline int cv_round_f(float v) { return (int)std::nearbyintf(v); }   // default mode: half-to-even
+
+inline void cv_axis(int src, int dst, bool is_x, std::vector<int> &i0, std::vector<int> &i1,
+                    std::vector<int> &c0, std::vector<int> &c1) {
+    const double inv_scale = (double)dst / (double)src;
+    const double scale = 1.0 / inv_scale;
+    i0.resize(dst); i1.resize(dst); c0.resize(dst); c1.resize(dst);
+    for (int d = 0; d < dst; ++d) {
+        float f = (float)((d + 0.5) * scale - 0.5);
+        int s = (int)std::floor(f);
+        f -= (float)s;
+        if (is_x) {                       // x axis: clamp index and zero the fraction
+            if (s < 0) { s = 0; f = 0.f; }
+            if (s >= src - 1) { s = src - 1; f = 0.f; }
+            i0[d] = s;
+            i1[d] = std::min(s + 1, src - 1);
+        } else {                          // y axis: keep coefficients, clip the row indices
+            i0[d] = std::min(std::max(s, 0), src - 1);
+            i1[d] = std::min(std::max(s + 1, 0), src - 1);
+        }
+        c0[d] = cv_round_f((1.f - f) * 2048.f);
+        c1[d] = cv_round_f(f * 2048.f);
+    }
+}
+
+// ingest workgroup: T threads produce band_rows output rows (band_rows * ow/4 <= T and the 2 * band_rows row jobs fit
+// the T/40 loader groups x 4 iterations).
+// Measured at N=1024, same box: 12 rows x 7 bands (3.5 rounds of 2048 resident workgroups) 46.0-46.7 us; 11 x 8 (4.0
+// rounds) 50-52; 10 x 9 53; and with wider workgroups whose grids are exact rounds - 320 thr x 14 rows, 384 x 18,
+// 512 x 21 - 50.2 / 49.2 / 48.5 us: the half-empty last round is not what limits this kernel.
+inline int k1_band_rows(int ow, int T = kThreads) { return std::max(1, std::min(2 * (T / 40), T / std::max(1, ow / 4))); }
+
+// What agx_create decides about K1 from obs_size alone (no knob read here).  The four screen layouts (whole / compact
+// screens, RGB / gray) share it: whole screens take the band12 form where band12_ok, compact screens where compact12_ok,
+// each only with band_rows == 12; everything else is the general band kernel (k_ingest<256> and its GRAY / COMPACT
+// forms), whose source rows come from the affine form on whole screens where y_affine and from the row table otherwise.
+struct K1Plan {
+    int y_affine = 0, y_mul = 0, y_add = 0, y_shift = 0;   // see IngestParams
+    bool adjacent = false;      // every x tap pair is (x0, x0 + 1)
+    bool pairs = false;         // every (y0, y1) pair disjoint and ascending: packed rows 2 dy, 2 dy + 1
+    bool band12_ok = false;     // 12-row bands all full, affine source rows, adjacent x taps, phase-2 reads inside the row + slack
+    bool compact12_ok = false;  // band12_ok && pairs
+    int band_rows = 0;          // output rows per 256-thread workgroup
+    int rows_touched = 0;
+};
+
+// the band12 form (k_ingest_full12 and its gray / compact / flexscan forms) or the general band kernel, for one screen layout
+// at the band height its launch uses
+inline bool k1_band12(const K1Plan &q, bool compact, int band_rows) {
+    return (compact ? q.compact12_ok : q.band12_ok) && band_rows == 12;
+}
+
+struct K1Host {
+    std::vector<int> x0, x1, a0, a1, y0, y1, b0, b1;
+    std::vector<int32_t> src_rows;     // the source rows the vertical resize reads, ascending
+    std::vector<int> py0, py1;         // y0 / y1 as indices into src_rows (compact screens)
+    K1Plan plan;
+};
+
+inline K1Host build_k1(int obs_h, int obs_w) {
+    K1Host h;
+    K1Plan &q = h.plan;
+    cv_axis(kRawW, obs_w, true, h.x0, h.x1, h.a0, h.a1);
+    cv_axis(kRawH, obs_h, false, h.y0, h.y1, h.b0, h.b1);
+    std::set<int> touched;
+    for (int i = 0; i < obs_h; ++i) {
+        touched.insert(h.y0[i]);
+        touched.insert(h.y1[i]);
+    }
+    q.rows_touched = (int)touched.size();
+    // compact screens: packed index of every touched source row, the y table in packed indices
+    h.src_rows.assign(touched.begin(), touched.end());
+    std::vector<int> packed_of(kRawH, -1);
+    for (size_t k = 0; k < h.src_rows.size(); ++k) packed_of[h.src_rows[k]] = (int)k;
+    h.py0.resize(obs_h);
+    h.py1.resize(obs_h);
+    q.pairs = true;
+    for (int i = 0; i < obs_h; ++i) {
+        h.py0[i] = packed_of[h.y0[i]];
+        h.py1[i] = packed_of[h.y1[i]];
+        q.pairs = q.pairs && h.py0[i] == 2 * i && h.py1[i] == 2 * i + 1;
+    }
+    // look for an exact integer form of the row table: y0 = (dy*mul + add) >> shift, y1 = min(y0+1, H-1)
+    for (int sh = 0; sh <= 12 && !q.y_affine; ++sh) {
+        const long mul = std::lround((double)kRawH / obs_h * (double)(1 << sh));
+        for (long add = -(1L << sh); add <= (1L << (sh + 1)) && !q.y_affine; ++add) {
+            bool ok = true;
+            for (int i = 0; i < obs_h && ok; ++i) {
+                const long v = (i * mul + add) >> sh;
+                ok = v >= 0 && v == h.y0[i] && std::min<long>(v + 1, kRawH - 1) == h.y1[i];
+            }
+            if (ok) {
+                q.y_affine = 1;
+                q.y_mul = (int)mul;
+                q.y_add = (int)add;
+                q.y_shift = sh;
+            }
+        }
+    }
+    q.adjacent = true;
+    for (int i = 0; i < obs_w; ++i) q.adjacent = q.adjacent && h.x1[i] == h.x0[i] + 1;
+    q.band12_ok = q.adjacent && q.y_affine && obs_h % 12 == 0 && (obs_w / 4) * 12 <= kThreads;
+    // phase 2 of the band12 form reads 8 bytes at byte (2 x0) & ~3 of a 320-byte gray row: never past the row + the slack
+    // band12_lds reserves
+    for (int i = 0; i < obs_w && q.band12_ok; ++i)
+        if (((2 * h.x0[i]) & ~3) + 8 > 2 * kRawW + 8) q.band12_ok = false;
+    q.compact12_ok = q.band12_ok && q.pairs;
+    q.band_rows = k1_band_rows(obs_w);
+    return h;
+}
 
 // ---- K4 resize_to_full form: composed operators per window size (agx_k4_flex3.h, agx_rows.h)
 struct Flex3Host {

@@ -511,7 +511,9 @@ class RingOracle:
         self.ring = [collections.deque([np.zeros(self.obs, np.uint8)] * frame_stack, maxlen=frame_stack)
                      for _ in range(n)]
 
-    def ingest(self, frames, nvalid, clear=None, skip=None):
+    def ingest(self, frames, nvalid, clear=None, skip=None, gray=False):
+        """frames: RGB screens u8[n, 2, 210, 160, 3], or with ``gray`` ALE's own grayscale screens u8[n, 2, 210, 160]
+        (``getScreenGrayscale``, what atari_env.py:74 hands to cv2.resize)."""
         frames = np.asarray(frames)
         for i in range(self.n):
             if skip is not None and skip[i]:
@@ -522,7 +524,8 @@ class RingOracle:
             nv = int(nvalid[i])
             obs = np.zeros(self.obs, np.uint8)
             for f in range(min(nv, 2)):
-                obs = np.maximum(obs, get_state_u8(frames[i, f], self.obs))
+                state = cv_resize_linear_u8(frames[i, f], self.obs) if gray else get_state_u8(frames[i, f], self.obs)
+                obs = np.maximum(obs, state)
             self.ring[i].append(obs)
 
     def stack_u8(self):

@@ -50,6 +50,17 @@ def unit64(u8):
     return (np.asarray(u8).astype(np.float32) / np.float32(255.0)).astype(np.float64)
 
 
+def tie_pixels():
+    """RGB triples on exact .5 luminance ties (2989r+5870g+1140b = 5000 mod 10000)."""
+    out = []
+    for r in range(0, 256, 5):
+        for g in range(256):
+            for b in range(0, 256, 2):
+                if (2989 * r + 5870 * g + 1140 * b) % 10000 == 5000:
+                    out.append((r, g, b))
+    return np.array(out, dtype=np.uint8)
+
+
 def golden_tol(case):
     """Goldens stored as float32 lose <= half an ulp of 1.0; float64 ones are exact."""
     return 1e-7 if case["outs"][0].dtype == np.float32 else 1e-12

@@ -9,6 +9,8 @@
 //        harness raw oh ow fh fw antialias      (k_fovea_flexible_raw3 tables: raw-crop / mask-out / packed forms)
 //        harness plan oh ow fh fw ph pw antialias resize|raw|mask
 //                                               which kernel form agx_create + the launch code select for each kind, and why
+//        harness k1plan obs                     which K1 ingest form each screen layout selects at obs x obs, and what it branches on
+//        harness k1tables obs                   the K1 tables of build_k1: x0 x1 a0 a1 y0 y1 b0 b1 and the source-row list
 #include <cstdio>
 #include <cstdlib>
 #include <random>
@@ -396,7 +398,59 @@ int run(int argc, char **argv) {
 
 }  // namespace plan
 
+// ---- K1 ingest: the plan build_k1 (agx_host_tables.h) hands agx_create, per screen layout, as the launch code of
+// agx_api.hip reads it with no knob set (agx_ingest, agx_ingest_gray_raw, ingest_compact: k1_band12 at plan.band_rows).
+//   form=band12 br=12 bands=B
+//   form=general br=R bands=B partial=P affine=A xclamp=X yclamp=Y
+// partial: the last band has fewer rows than br; affine: source rows from the integer form (whole screens only - compact
+// screens always read the packed row table); xclamp / yclamp: some tap pair is one source column / row twice.
+static int k1plan_main(int argc, char **argv) {
+    if (argc < 3) return 2;
+    const int o = atoi(argv[2]);
+    if (o < 4 || o > 1024 || (o & 3)) return 2;             // not a size agx_create accepts (k1tables: the same)
+    const K1Host h = build_k1(o, o);
+    const K1Plan &q = h.plan;
+    bool xclamp = false, yclamp = false;
+    for (int i = 0; i < o; ++i) {
+        xclamp = xclamp || h.x0[i] == h.x1[i];
+        yclamp = yclamp || h.y0[i] == h.y1[i];
+    }
+    const int br = q.band_rows, bands = (o + br - 1) / br;
+    const char *names[4] = {"rgb", "gray", "rgb-compact", "gray-compact"};
+    for (int k = 0; k < 4; ++k) {
+        const bool compact = k >= 2;
+        if (k1_band12(q, compact, br)) printf("%s form=band12 br=%d bands=%d\n", names[k], br, bands);
+        else
+            printf("%s form=general br=%d bands=%d partial=%d affine=%d xclamp=%d yclamp=%d\n", names[k], br, bands, o % br != 0,
+                   !compact && q.y_affine, xclamp, yclamp);
+    }
+    printf("affine mul=%d add=%d shift=%d ok=%d\n", q.y_mul, q.y_add, q.y_shift, q.y_affine);
+    printf("flags adjacent=%d pairs=%d band12_ok=%d compact12_ok=%d rows=%d\n", q.adjacent, q.pairs, q.band12_ok, q.compact12_ok,
+           q.rows_touched);
+    return 0;
+}
+
+static void print_row(const char *key, const std::vector<int> &v) {
+    printf("%s", key);
+    for (int x : v) printf(" %d", x);
+    printf("\n");
+}
+
+static int k1tables_main(int argc, char **argv) {
+    if (argc < 3) return 2;
+    const int o = atoi(argv[2]);
+    if (o < 4 || o > 1024 || (o & 3)) return 2;
+    const K1Host h = build_k1(o, o);
+    print_row("x0", h.x0); print_row("x1", h.x1); print_row("a0", h.a0); print_row("a1", h.a1);
+    print_row("y0", h.y0); print_row("y1", h.y1); print_row("b0", h.b0); print_row("b1", h.b1);
+    print_row("rows", std::vector<int>(h.src_rows.begin(), h.src_rows.end()));
+    print_row("py0", h.py0); print_row("py1", h.py1);
+    return 0;
+}
+
 int main(int argc, char **argv) {
+    if (argc > 1 && !strcmp(argv[1], "k1plan")) return k1plan_main(argc, argv);
+    if (argc > 1 && !strcmp(argv[1], "k1tables")) return k1tables_main(argc, argv);
     if (argc > 1 && !strcmp(argv[1], "plan")) return plan::run(argc, argv);
     if (argc > 1 && !strcmp(argv[1], "per")) return per_main(argc, argv);
     if (argc > 1 && !strcmp(argv[1], "raw")) return raw_main(argc, argv);

@@ -11,6 +11,7 @@ import pytest
 import torch
 
 from golden_util import fovea_case_names, load_fovea, unit64
+from golden_util import tie_pixels as _tie_pixels
 from oracle import oracle as O
 
 pytestmark = pytest.mark.gpu
@@ -62,17 +63,6 @@ def test_unit_division_all_256_values_bit_exact(dev):
 
 
 # ---------------------------------------------------------------- K1
-def _tie_pixels():
-    """RGB triples on exact .5 luminance ties (2989r+5870g+1140b = 5000 mod 10000)."""
-    out = []
-    for r in range(0, 256, 5):
-        for g in range(256):
-            for b in range(0, 256, 2):
-                if (2989 * r + 5870 * g + 1140 * b) % 10000 == 5000:
-                    out.append((r, g, b))
-    return np.array(out, dtype=np.uint8)
-
-
 def test_ingest_matches_oracle_sequence(dev):
     N, fs = 7, 4
     rng = np.random.default_rng(42)
