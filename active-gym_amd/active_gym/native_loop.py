@@ -154,19 +154,38 @@ class NativeStepLoop:
         self._check(self._lib.agx_loop_reset_envs(self._h, idx.ctypes.data, len(idx), noops.ctypes.data, self._ptr(obs), self._ptr(loc),
                                                   self._ptr(res), self._stream()))
 
-    def step(self, motor, action: Optional[torch.Tensor], action_dt: int, action_type: Optional[torch.Tensor], obs: torch.Tensor,
-             loc: Optional[torch.Tensor], res: Optional[torch.Tensor]):
-        """Returns (reward f64[N], raw f64[N], done bool[N], done_idx i32[k], final_obs [k, ...] | None, final_loc | None,
-        final_res | None) - host arrays are copies, device tensors are views of loop-owned buffers valid until the next step."""
+    @property
+    def handle(self):
+        """The agx_loop* (for the entry points of other headers that take one: active_gym/native_hostout.py)."""
+        return self._h
+
+    def check(self, rc):
+        """Raise for a non-zero return code of an entry point that took this loop (or for a pending callback error)."""
+        self._check(rc)
+
+    def call_step(self, fn, motor, action: Optional[torch.Tensor], action_dt: int, action_type: Optional[torch.Tensor],
+                  obs: torch.Tensor, loc: Optional[torch.Tensor], res: Optional[torch.Tensor], *extra):
+        """One step through ``fn`` - agx_loop_step, or an entry point with its leading arguments (agx_loop_step_host:
+        ``extra`` follows the stream) - and the host part of its result: (reward f64[N], raw f64[N], done bool[N], done_idx
+        i32[k], the AgxLoopResult).  The one place that marshals a step's arguments and unpacks its host arrays."""
         self._motor[:] = motor
         r = self._res
-        self._check(self._lib.agx_loop_step(self._h, self._motor_ptr, self._ptr(action), int(action_dt), self._ptr(action_type),
-                                            self._ptr(obs), self._ptr(loc), self._ptr(res), C.byref(r), self._stream()))
-        n, k = self.n, int(r.n_done)
+        self._check(fn(self._h, self._motor_ptr, self._ptr(action), int(action_dt), self._ptr(action_type), self._ptr(obs),
+                       self._ptr(loc), self._ptr(res), C.byref(r), self._stream(), *extra))
+        k = int(r.n_done)
         reward = self._host("reward", r.reward, np.float64).copy()
         raw = self._host("raw", r.raw, np.float64).copy()
         done = self._host("done", r.done, np.uint8).astype(bool)
         idx = self._host("done_idx", r.done_idx, np.int32)[:k].copy() if k else np.zeros(0, np.int32)
+        self.h2d_bytes = int(r.h2d_bytes)
+        return reward, raw, done, idx, r
+
+    def step(self, motor, action: Optional[torch.Tensor], action_dt: int, action_type: Optional[torch.Tensor], obs: torch.Tensor,
+             loc: Optional[torch.Tensor], res: Optional[torch.Tensor]):
+        """Returns (reward f64[N], raw f64[N], done bool[N], done_idx i32[k], final_obs [k, ...] | None, final_loc | None,
+        final_res | None) - host arrays are copies, device tensors are views of loop-owned buffers valid until the next step."""
+        reward, raw, done, idx, r = self.call_step(self._lib.agx_loop_step, motor, action, action_dt, action_type, obs, loc, res)
+        n, k = self.n, len(idx)
         fo = fl = fr = None
         if k and r.d_final_obs:
             # the terminal rows are elements of the observation's type (bfloat16 has no array-interface type string: int16 bits)
@@ -178,7 +197,6 @@ class NativeStepLoop:
                 fl = self._device("final_loc", r.d_final_loc, (n, 2), "<i4")[:k]
             if r.d_final_res:
                 fr = self._device("final_res", r.d_final_res, (n, 2), "<i4")[:k]
-        self.h2d_bytes = int(r.h2d_bytes)
         return reward, raw, done, idx, fo, fl, fr
 
     # The loop's result arrays and side buffers are allocated once in agx_loop_create and never move: ONE NumPy / torch view per

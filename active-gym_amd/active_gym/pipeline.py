@@ -173,6 +173,14 @@ class ObsPipeline:
         k = {"ingest": nat.K_INGEST, "fovea": nat.K_FOVEA}[kernel]
         nat.check(self._lib.agx_profile_next(self._ctx, k, C.c_void_p(start.cuda_event), C.c_void_p(stop.cuda_event)), self._ctx)
 
+    def env_range(self, lo: int = 0, n: Optional[int] = None):
+        """Until changed, ingest* (the Atari forms), observe_full, fovea and fovea_reset act on envs [lo, lo + n) only and leave
+        every other env's state and output rows untouched (agx_env_range, include/agx_hostout.h); tensors keep their whole-batch
+        shapes.  ``env_range()`` restores the whole batch."""
+        from . import native_hostout as nh
+        n = self.num_envs - int(lo) if n is None else int(n)
+        nat.check(nh.lib().agx_env_range(self._ctx, int(lo), n), self._ctx)
+
     # ------------------------------------------------------------------ K1
     def ingest(self, frames: torch.Tensor, cmd: torch.Tensor):
         """frames u8[N,2,210,160,3] RGB, cmd u8[N] (nvalid | CMD_CLEAR | CMD_SKIP)."""

@@ -106,10 +106,15 @@ class _HostObsPool:
 class AtariVecEnv:
     """N envs of one kind.  ``args`` is an ``AtariEnvArgs``; extra optional attributes:
     ``frame_source`` ("ale" | "synthetic" | factory), ``device`` (None -> NumPy outputs on the host like
-    the reference; a cuda device -> torch tensors that stay in HBM), ``antialias``, ``num_workers``."""
+    the reference; a cuda device -> torch tensors that stay in HBM), ``antialias``, ``num_workers``,
+    ``host_obs_chunks`` (C > 0 with ``device=None`` and a native frame source: step() runs in the native loop and
+    brings the observations home in C env chunks, each chunk's device-to-host copy under the next chunk's
+    host-to-device copy and kernels; ``env.host_obs_chunks`` is the value in effect, 0 = the unchunked path)."""
 
     _loop = None             # NativeStepLoop when the native step loop drives this env (subclasses with their own source: never)
     _want_loop = False
+    host_obs_chunks = 0      # chunks of the host-output step in effect (args.host_obs_chunks where its conditions hold, else 0)
+    _host_step = None        # native_hostout.HostOutStep when host_obs_chunks > 0
 
     def __init__(self, args, num_envs: int, kind: str = "fixed", env_offset: int = 0, noop_fn=None,
                  autoreset: bool = True, noop_per_env: bool = False):
@@ -149,6 +154,7 @@ class AtariVecEnv:
             if self._loop is not None:
                 self._loop.close()
                 self._loop = None
+                self._host_step = None
             self.pipe.close()
             self.kind = kind
             self._build_pipeline()
@@ -292,10 +298,17 @@ class AtariVecEnv:
         # step() is then ONE C call.  Used with the native runner and device outputs (args.native_loop = False keeps the Python
         # loop below); the chunked-H2D form and the ragged packed observations stay on the Python loop.
         self._loop = None
-        self._want_loop = bool(native and not self._numpy_out and getattr(args, "native_loop", True)
-                               and not int(getattr(args, "h2d_chunk_envs", 0) or 0)
-                               and not (self.kind == "flexible" and not (bool(args.mask_out) or bool(args.resize_to_full))
-                                        and getattr(args, "ragged_obs", "padded") == "packed"))
+        loop_ok = bool(native and getattr(args, "native_loop", True)
+                       and not int(getattr(args, "h2d_chunk_envs", 0) or 0)
+                       and not (self.kind == "flexible" and not (bool(args.mask_out) or bool(args.resize_to_full))
+                                and getattr(args, "ragged_obs", "padded") == "packed"))
+        # Host outputs stay on the Python loop unless args.host_obs_chunks = C > 0 asks for the chunked host-output step
+        # (agx_loop_step_host, include/agx_hostout.h: gray Atari contexts, padded observations)
+        hc = int(getattr(args, "host_obs_chunks", 0) or 0)
+        if hc < 0:
+            raise ValueError(f"host_obs_chunks must be >= 0, got {hc}")
+        self.host_obs_chunks = hc if (loop_ok and self._numpy_out and self.channels == 1) else 0
+        self._want_loop = loop_ok and (not self._numpy_out or self.host_obs_chunks > 0)
         if not self._want_loop:
             with hostplan.bound_to(self.host_plan["cpus"] and self.host_plan["domain"]):
                 self._alloc_staging(shape, rows, px)
@@ -321,6 +334,10 @@ class AtariVecEnv:
             # its pinned staging is allocated inside: bound to this rank's CPUs (first touch on the GPU's NUMA node)
             with hostplan.bound_to(self.host_plan["cpus"] and self.host_plan["domain"]):
                 self._loop = NativeStepLoop(self.pipe, self.runner, gray=self._gray, compact=self._compact, autoreset=self.autoreset)
+                self._host_step = None
+                if self.host_obs_chunks > 0:
+                    from .native_hostout import HostOutStep
+                    self._host_step = HostOutStep(self._loop, self.host_obs_chunks)      # (its pinned fov rows: same binding)
 
     def _alloc_staging(self, shape, rows, px):
         # Two pinned staging sets (screens, command bytes, copy-done event), used alternately: with device outputs step()
@@ -387,6 +404,7 @@ class AtariVecEnv:
         if getattr(self, "_loop", None) is not None:
             self._loop.close()
             self._loop = None
+            self._host_step = None
         self.runner.close()
         self.pipe.close()
 
@@ -529,6 +547,18 @@ class AtariVecEnv:
 
     # below 1 MB of observations (the single-env wrappers: 113 KB) a pageable copy is as cheap as the pool's bookkeeping
     _HOST_POOL_MIN_ELEMS = 1 << 18
+
+    def _take_host_obs(self, obs):
+        """The pinned destination of a chunked host-output step: the next buffer of the args.copy_obs = False pair, or one from
+        the pool (None when its budget is spent, or there is no pool: that call takes the unchunked copy)."""
+        if self._pinned_host_obs:
+            if self._h_obs is None or tuple(self._h_obs[0].shape) != tuple(obs.shape):
+                self._h_obs = [torch.empty(tuple(obs.shape), dtype=obs.dtype, pin_memory=True) for _ in range(2)]
+            self._h_obs_i ^= 1
+            return self._h_obs[self._h_obs_i]
+        if self._host_pool is not None:
+            return self._host_pool.take(obs.shape, obs.dtype)
+        return None
 
     def _ret_obs(self, obs):
         if self._ragged_packed:
@@ -715,8 +745,17 @@ class AtariVecEnv:
             if sens.dtype not in _DT:
                 raise TypeError(f"sensory action dtype {sens.dtype} not supported (f32/f64/i32/i64)")
             dt = _DT[sens.dtype]
-        reward, raw, done, idx, fo, fl, fr = self._loop.step(motor, sens, dt, stype, obs, self._loc if fov else None,
-                                                             self._res if self.kind == "flexible" else None)
+        d_loc, d_res = self._loc if fov else None, self._res if self.kind == "flexible" else None
+        # host outputs in env chunks (args.host_obs_chunks): straight into a pinned buffer, observations, fov rows and terminal
+        # rows as NumPy; without a pinned destination (pool budget spent) this call is the unchunked step + copy
+        h = self._take_host_obs(obs) if self._host_step is not None else None
+        h_loc = h_res = None
+        if h is not None:
+            reward, raw, done, idx, fo, fl, fr, h_loc, h_res = self._host_step.step(motor, sens, dt, stype, obs, d_loc, d_res, h)
+        else:
+            reward, raw, done, idx, fo, fl, fr = self._loop.step(motor, sens, dt, stype, obs, d_loc, d_res)
+            if self._numpy_out:
+                fo, fl, fr = (None if t is None else t.cpu().numpy() for t in (fo, fl, fr))
         self.ep_len += 1
         self.cumulative_reward += raw                   # unclipped, fov_env.py:62
         truncated = np.zeros(n, bool)                   # always False, atari_env.py:145
@@ -726,12 +765,18 @@ class AtariVecEnv:
         if self.autoreset and k:
             # terminal observations / infos of the envs that ended an episode: rows of the loop's side buffers (cloned: the loop
             # reuses them next step), handed out as views like the Python loop's index_select rows
-            fo = fo.clone()
             gathered = {}
-            if fl is not None:
-                gathered["fov_loc"] = fl.to(torch.int64)
-            if fr is not None:
-                gathered["fov_res"] = fr.to(torch.int64)
+            if self._numpy_out:                     # NumPy rows (already copies), int64 like the reference's infos
+                if fl is not None:
+                    gathered["fov_loc"] = fl.astype(np.int64)
+                if fr is not None:
+                    gathered["fov_res"] = fr.astype(np.int64)
+            else:
+                fo = fo.clone()
+                if fl is not None:
+                    gathered["fov_loc"] = fl.to(torch.int64)
+                if fr is not None:
+                    gathered["fov_res"] = fr.to(torch.int64)
             final_obs = np.empty(n, dtype=object)
             final_info = np.empty(n, dtype=object)
             for j, i in enumerate(idx):
@@ -749,15 +794,23 @@ class AtariVecEnv:
             info["ep_len"][idx] = 0
         if fov:
             # self._loc / self._res: the step's values, overwritten by the masked re-observation for the envs that were reset
-            info["fov_loc"] = self._loc.to(torch.int64)
-            if self.kind == "flexible":
-                info["fov_res"] = self._res.to(torch.int64)
+            if self._numpy_out:
+                info["fov_loc"] = (h_loc if h_loc is not None else self._loc.cpu().numpy()).astype(np.int64)
+                if self.kind == "flexible":
+                    info["fov_res"] = (h_res if h_res is not None else self._res.cpu().numpy()).astype(np.int64)
+            else:
+                info["fov_loc"] = self._loc.to(torch.int64)
+                if self.kind == "flexible":
+                    info["fov_res"] = self._res.to(torch.int64)
         infos = self._with_masks(self._extra_info(info), n)
         if final is not None:
             infos["final_observation"] = final[0]
             infos["_final_observation"] = done.copy()
             infos["final_info"] = final[1]
             infos["_final_info"] = done.copy()
+        if h is not None:
+            ret = h.numpy() if self._pinned_host_obs else self._host_pool.hand_out(h)
+            return ret, reward, done, truncated, infos
         return self._ret_obs(obs), reward, done, truncated, infos
 
     def reset_envs(self, idx):

@@ -19,6 +19,7 @@
 #include "agx_kernels.h"
 #include "agx_host_tables.h"
 #include "agx_device_guard.h"
+#include "agx_range.h"
 
 using namespace agx;
 
@@ -32,6 +33,7 @@ struct agx_ctx {
     int32_t *res[2] = {nullptr, nullptr};
     int cur_head = 0;
     int cur_fov = 0;
+    int rng_lo = 0, rng_n = 0;    // agx_env_range: the envs the ranged entry points act on ([0, num_envs) after agx_create)
     int2 *in_xtab = nullptr;   // K1 tables
     int4 *in_ytab = nullptr;
     int2 *in_xtab12 = nullptr; // K1 band12 form: {2 * x0, (a0 | a1 << 16) << 4} / {b0 << 8, b1 << 8}
@@ -324,6 +326,34 @@ size_t generic_lds(const agx_config &c) {
 
 constexpr size_t kMaxLds = 160 * 1024;   // gfx950: a workgroup may take the whole 160 KiB of its CU
 
+// ---- env range (agx_env_range, include/agx_hostout.h; agx_range.h says how it reaches the kernels)
+bool full_range(const agx_ctx *ctx) { return ctx->rng_lo == 0 && ctx->rng_n == ctx->cfg.num_envs; }
+int refuse_range(agx_ctx *ctx, const char *who) {
+    return fail(ctx, AGX_E_STATE, "%s: acts on the whole batch only; the context's env range is [%d, %d) (agx_env_range)", who,
+                ctx->rng_lo, ctx->rng_lo + ctx->rng_n);
+}
+// the out-of-range envs' entries of a double-buffered state array pair, from the buffer a ranged launch read to the one it wrote
+void range_carry(const agx_ctx *ctx, const int32_t *src0, int32_t *dst0, const int32_t *src1, int32_t *dst1, int words, hipStream_t st) {
+    if (full_range(ctx)) return;
+    RangeCarryParams q;
+    q.src[0] = src0; q.dst[0] = dst0; q.src[1] = src1; q.dst[1] = dst1;
+    q.words = words;
+    q.lo = ctx->rng_lo; q.n = ctx->rng_n; q.total = ctx->cfg.num_envs;
+    hipLaunchKernelGGL(k_range_carry, dim3((q.total * words + kThreads - 1) / kThreads), dim3(kThreads), 0, st, q);
+}
+
+// the context's env range on an ingest launch: base pointers advanced by rng_lo envs (the grid's env dimension is rng_n);
+// env_bytes = the two screens of one env in this entry point's layout
+template <class P>
+void ingest_range(const agx_ctx *ctx, P &p, const uint8_t *P::*frames, size_t env_bytes) {
+    const size_t lo = (size_t)ctx->rng_lo;
+    p.*frames += lo * env_bytes;
+    p.cmd += lo;
+    p.ring += lo * (size_t)ctx->cfg.frame_stack * ctx->planes * ((size_t)ctx->cfg.obs_h * ctx->cfg.obs_w);
+    p.head_in += lo;
+    p.head_out += lo;
+}
+
 }  // namespace
 
 extern "C" {
@@ -437,6 +467,7 @@ int agx_create(const agx_config *cfg, agx_ctx **out) {
     ctx->cfg = c;
     ctx->obs_type = obs_type;
     ctx->planes = planes;
+    ctx->rng_n = c.num_envs;
     ctx->tune.generic = env_int("AGX_FOVEA_GENERIC");
     ctx->tune.no_full = env_int("AGX_INGEST_NO_FULL");
     ctx->tune.flex_v2 = env_int("AGX_FLEX_V2");
@@ -714,6 +745,10 @@ static IngestParams ingest_params(agx_ctx *ctx, const uint8_t *d_frames, const u
 #endif
     return p;
 }
+// after a ranged ingest launch, in front of the head flip
+static void ingest_carry(const agx_ctx *ctx, void *stream) {
+    range_carry(ctx, ctx->head[ctx->cur_head], ctx->head[ctx->cur_head ^ 1], nullptr, nullptr, 1, S(stream));
+}
 
 // agx_ingest_gray_raw: the plan's 256-thread bands (AGX_INGEST_BAND_ROWS of the experiments build narrows them as it does the
 // RGB ingest's; the other opt-in variants are RGB-only)
@@ -739,7 +774,9 @@ int agx_ingest(agx_ctx *ctx, const uint8_t *d_frames, const uint8_t *d_cmd, void
                     "agx_ingest: obs_size (%d,%d) is not square; the reference hands obs_size to cv2.resize as "
                     "(width,height) and fails on non-square sizes (atari_env.py:74,126)", c.obs_h, c.obs_w);
     DeviceGuard g(c.device);
-    const IngestParams p = ingest_params(ctx, d_frames, d_cmd);
+    IngestParams p = ingest_params(ctx, d_frames, d_cmd);
+    ingest_range(ctx, p, &IngestParams::frames, (size_t)2 * kRawFrameBytes);
+    const int en = ctx->rng_n;             // envs of the launch (num_envs unless agx_env_range narrowed it)
     const int bands = p.nbands;
     const size_t lds = ingest_lds(ctx);
 #ifdef AGX_EXPERIMENTS
@@ -754,19 +791,19 @@ int agx_ingest(agx_ctx *ctx, const uint8_t *d_frames, const uint8_t *d_cmd, void
                          rpw >= 1 && rpw <= 3 && rpw * (c.obs_w / 4) <= 64;
     if (wave_ok) {
         const size_t slice = ((sizeof(int2) * c.obs_w + (size_t)2 * rpw * kRawW * 2) + 15) & ~(size_t)15;
-        hipLaunchKernelGGL(k_ingest_wave, dim3(bands, c.num_envs), dim3(256), 4 * slice, S(stream), p);
+        hipLaunchKernelGGL(k_ingest_wave, dim3(bands, en), dim3(256), 4 * slice, S(stream), p);
     } else if (pipe_parts > 0 && ctx->ingest_t == 256) {
         const int parts = std::min(pipe_parts, bands);
         const size_t lds2 = sizeof(int4) * c.obs_h + sizeof(int2) * c.obs_w + (size_t)2 * (2 * ctx->band_rows * 2 * kRawW);
-        hipLaunchKernelGGL(k_ingest_pipe<256>, dim3(parts, c.num_envs), dim3(256), lds2, S(stream), p);
+        hipLaunchKernelGGL(k_ingest_pipe<256>, dim3(parts, en), dim3(256), lds2, S(stream), p);
     } else if (ctx->ingest_t == 128)
-        hipLaunchKernelGGL(k_ingest<128>, dim3(bands, c.num_envs), dim3(128), lds, S(stream), p);
+        hipLaunchKernelGGL(k_ingest<128>, dim3(bands, en), dim3(128), lds, S(stream), p);
     // (same box, N=1024: 37.5-37.9 us against 37.9-38.2 for the one-band form - K1 is VALU-issue- and HBM-limited, not
     //  limited by the load-free tail of a workgroup - so it stays opt-in)
     else if (ctx->tune.no_full == 0 && ctx->tune.pair12 != 0 && ctx->tune.band_rows == 0 && ctx->tune.ingest_t == 0 &&
              ctx->k1.y_affine && ctx->band_rows == 12 && c.obs_h % 12 == 0 && (c.obs_w / 4) * 12 <= kThreads)
-        AGX_LAUNCH(0, k_ingest_pair12, dim3(bands, (c.num_envs + 1) / 2), dim3(256), lds + (size_t)2 * 12 * 2 * kRawW, S(stream), p,
-                   (int)c.num_envs);
+        AGX_LAUNCH(0, k_ingest_pair12, dim3(bands, (en + 1) / 2), dim3(256), lds + (size_t)2 * 12 * 2 * kRawW, S(stream), p,
+                   en);
     else launched = false;
     if (!launched)
 #endif
@@ -774,10 +811,11 @@ int agx_ingest(agx_ctx *ctx, const uint8_t *d_frames, const uint8_t *d_cmd, void
         // the headline form where its plan applies (12-row bands all full, affine source rows, adjacent x taps), the general
         // band kernel otherwise
         if (ctx->tune.no_full == 0 && k1_band12(ctx->k1, false, ctx->band_rows))
-            AGX_LAUNCH(0, k_ingest_full12, dim3(bands, c.num_envs), dim3(256), band12_lds(ctx), S(stream), p);
+            AGX_LAUNCH(0, k_ingest_full12, dim3(bands, en), dim3(256), band12_lds(ctx), S(stream), p);
         else
-            AGX_LAUNCH(0, k_ingest<256>, dim3(bands, c.num_envs), dim3(256), lds, S(stream), p);
+            AGX_LAUNCH(0, k_ingest<256>, dim3(bands, en), dim3(256), lds, S(stream), p);
     }
+    ingest_carry(ctx, stream);
     AGX_HIP(ctx, hipGetLastError());
     ctx->cur_head ^= 1;
     return AGX_OK;
@@ -792,13 +830,15 @@ int agx_ingest_gray_raw(agx_ctx *ctx, const uint8_t *d_gray, const uint8_t *d_cm
         return fail(ctx, AGX_E_STATE, "agx_ingest_gray_raw needs a square obs_size (cv2.resize takes (width, height): atari_env.py:74)");
     DeviceGuard g(c.device);
     IngestParams p = ingest_params(ctx, d_gray, d_cmd);
+    ingest_range(ctx, p, &IngestParams::frames, (size_t)2 * kRawH * kRawW);
     p.band_rows = gray_band_rows(ctx);
     p.nbands = (c.obs_h + p.band_rows - 1) / p.band_rows;
     const size_t lds = sizeof(int4) * p.band_rows + sizeof(int2) * c.obs_w + (size_t)2 * p.band_rows * 2 * kRawW;
     if (ctx->tune.no_full == 0 && k1_band12(ctx->k1, false, p.band_rows))
-        AGX_LAUNCH(0, k_ingest_grayraw_full12, dim3(p.nbands, c.num_envs), dim3(kThreads), band12_lds(ctx), S(stream), p);
+        AGX_LAUNCH(0, k_ingest_grayraw_full12, dim3(p.nbands, ctx->rng_n), dim3(kThreads), band12_lds(ctx), S(stream), p);
     else
-        AGX_LAUNCH(0, k_ingest_grayraw, dim3(p.nbands, c.num_envs), dim3(kThreads), lds, S(stream), p);
+        AGX_LAUNCH(0, k_ingest_grayraw, dim3(p.nbands, ctx->rng_n), dim3(kThreads), lds, S(stream), p);
+    ingest_carry(ctx, stream);
     AGX_HIP(ctx, hipGetLastError());
     ctx->cur_head ^= 1;
     return AGX_OK;
@@ -823,13 +863,14 @@ static int ingest_compact(agx_ctx *ctx, const uint8_t *d_rows, const uint8_t *d_
     DeviceGuard g(c.device);
     IngestParams p = ingest_params(ctx, d_rows, d_cmd);
     p.src_rows = (int32_t)ctx->src_rows.size();
+    ingest_range(ctx, p, &IngestParams::frames, (size_t)2 * ctx->src_rows.size() * kRawW * (gray ? 1 : 3));
     p.ytab = ctx->in_ytab_c;             // packed row indices
     p.y_affine = 0;
     const int br = ctx->k1.band_rows;    // always the default 256-thread band form
     p.band_rows = br;
     p.nbands = (c.obs_h + br - 1) / br;
     const size_t lds = sizeof(int4) * br + sizeof(int2) * c.obs_w + (size_t)2 * br * 2 * kRawW;
-    const dim3 grid(p.nbands, c.num_envs), block(kThreads);
+    const dim3 grid(p.nbands, ctx->rng_n), block(kThreads);
     if (ctx->tune.no_full == 0 && k1_band12(ctx->k1, true, br)) {
         if (gray) AGX_LAUNCH(0, k_ingest_grayraw_full12_compact, grid, block, band12_lds(ctx), S(stream), p);
         else AGX_LAUNCH(0, k_ingest_full12_compact, grid, block, band12_lds(ctx), S(stream), p);
@@ -837,6 +878,7 @@ static int ingest_compact(agx_ctx *ctx, const uint8_t *d_rows, const uint8_t *d_
         if (gray) AGX_LAUNCH(0, k_ingest_grayraw_compact, grid, block, lds, S(stream), p);
         else AGX_LAUNCH(0, k_ingest_compact, grid, block, lds, S(stream), p);
     }
+    ingest_carry(ctx, stream);
     AGX_HIP(ctx, hipGetLastError());
     ctx->cur_head ^= 1;
     return AGX_OK;
@@ -864,9 +906,11 @@ int agx_ingest_gray(agx_ctx *ctx, const uint8_t *d_small, const uint8_t *d_cmd, 
     p.oh = c.obs_h;
     p.ow = c.obs_w;
     p.fs = c.frame_stack;
+    ingest_range(ctx, p, &IngestGrayParams::small, (size_t)2 * c.obs_h * c.obs_w);
     const int words = c.obs_h * c.obs_w / 4;
-    hipLaunchKernelGGL(k_ingest_gray, dim3((words + kThreads - 1) / kThreads, c.num_envs), dim3(kThreads), 0,
+    hipLaunchKernelGGL(k_ingest_gray, dim3((words + kThreads - 1) / kThreads, ctx->rng_n), dim3(kThreads), 0,
                        S(stream), p);
+    ingest_carry(ctx, stream);
     AGX_HIP(ctx, hipGetLastError());
     ctx->cur_head ^= 1;
     return AGX_OK;
@@ -875,6 +919,7 @@ int agx_ingest_gray(agx_ctx *ctx, const uint8_t *d_small, const uint8_t *d_cmd, 
 int agx_ingest_rgb(agx_ctx *ctx, const uint8_t *d_frames, const uint8_t *d_cmd, int gray_mode, void *stream) {
     if (!ctx) return AGX_E_INVALID;
     if (!d_frames || !d_cmd) return fail(ctx, AGX_E_INVALID, "agx_ingest_rgb: null buffer");
+    if (!full_range(ctx)) return refuse_range(ctx, "agx_ingest_rgb");
     const agx_config &c = ctx->cfg;
     DeviceGuard g(c.device);
     IngestRgbParams p;
@@ -927,7 +972,15 @@ static int stack_launch(agx_ctx *ctx, int which, const uint8_t *in_u8, uint8_t *
     p.out_f32 = out_f32;
     p.words = c.obs_h * c.obs_w / 4;
     p.fs = c.frame_stack;
-    const dim3 grid((p.words + kThreads - 1) / kThreads, c.frame_stack * ctx->planes, c.num_envs);
+    int en = c.num_envs;
+    if (which == 2) {                          // agx_observe_full acts on the context's env range (get / set: the whole batch)
+        const size_t lo = (size_t)ctx->rng_lo, row = (size_t)c.frame_stack * ctx->planes * c.obs_h * c.obs_w;
+        p.ring += lo * row;
+        p.head += lo;
+        p.out_f32 = reinterpret_cast<float *>(reinterpret_cast<char *>(out_f32) + lo * row * obs_elem_bytes(ctx->obs_type));
+        en = ctx->rng_n;
+    }
+    const dim3 grid((p.words + kThreads - 1) / kThreads, c.frame_stack * ctx->planes, en);
     with_planes(ctx->planes, [&](auto pc) {
         constexpr int NC = decltype(pc)::value;
         if (which == 0)
@@ -969,15 +1022,15 @@ int agx_fovea_reset(agx_ctx *ctx, const uint8_t *d_mask, void *stream) {
     if (!has_fovea(c)) return fail(ctx, AGX_E_STATE, "agx_fovea_reset: context has no fovea (AGX_KIND_BASE)");
     DeviceGuard g(c.device);
     FovResetParams p;
-    p.mask = d_mask;
-    p.loc = ctx->loc[ctx->cur_fov];
-    p.res = ctx->res[ctx->cur_fov];
+    p.mask = d_mask ? d_mask + ctx->rng_lo : nullptr;
+    p.loc = ctx->loc[ctx->cur_fov] + 2 * (size_t)ctx->rng_lo;
+    p.res = ctx->res[ctx->cur_fov] + 2 * (size_t)ctx->rng_lo;
     p.init_r = ctx->init_r;
     p.init_c = ctx->init_c;
     p.fh = c.fov_h;
     p.fw = c.fov_w;
-    p.n = c.num_envs;
-    hipLaunchKernelGGL(k_fovea_reset, dim3((c.num_envs + kThreads - 1) / kThreads), dim3(kThreads), 0, S(stream), p);
+    p.n = ctx->rng_n;
+    hipLaunchKernelGGL(k_fovea_reset, dim3((p.n + kThreads - 1) / kThreads), dim3(kThreads), 0, S(stream), p);
     AGX_HIP(ctx, hipGetLastError());
     return AGX_OK;
 }
@@ -1049,6 +1102,35 @@ static FovParams fov_params(agx_ctx *ctx, const void *d_action, int dt, const in
 #endif
     return p;
 }
+// the context's env range on a fovea launch: every per-env base pointer advanced by rng_lo envs (the grid's env dimension is
+// rng_n); the observation row is that of agx_obs_shape in the context's element type
+static void fov_range(const agx_ctx *ctx, FovParams &p) {
+    const size_t lo = (size_t)ctx->rng_lo;
+    if (lo == 0) return;
+    const agx_config &c = ctx->cfg;
+    const size_t planes = (size_t)c.frame_stack * ctx->planes, px = (size_t)c.obs_h * c.obs_w;
+    const bool crop = c.kind == AGX_KIND_FIXED && c.out_mode == AGX_OUT_RAW;
+    const size_t row_bytes = planes * (crop ? (size_t)c.fov_h * c.fov_w : px) * obs_elem_bytes(ctx->obs_type);
+    const bool wide = p.action_dt == AGX_DT_F64 || p.action_dt == AGX_DT_I64;
+    p.ring += lo * planes * px;
+    p.head += lo;
+    p.loc_in += 2 * lo;
+    p.loc_out += 2 * lo;
+    p.res_in += 2 * lo;
+    p.res_out += 2 * lo;
+    if (p.action) p.action = static_cast<const char *>(p.action) + lo * (wide ? 16 : 8);
+    if (p.action_type) p.action_type += lo;
+    if (p.mask) p.mask += lo;
+    p.obs = reinterpret_cast<float *>(reinterpret_cast<char *>(p.obs) + lo * row_bytes);
+    if (p.user_loc) p.user_loc += 2 * lo;
+    if (p.user_res) p.user_res += 2 * lo;
+}
+// after a ranged fovea launch, in front of the fov flip: fov_loc of the out-of-range envs, and fov_res where the kind writes it
+static void fov_carry(const agx_ctx *ctx, void *stream) {
+    const bool flex = ctx->cfg.kind == AGX_KIND_FLEXIBLE;
+    range_carry(ctx, ctx->loc[ctx->cur_fov], ctx->loc[ctx->cur_fov ^ 1], flex ? ctx->res[ctx->cur_fov] : nullptr,
+                flex ? ctx->res[ctx->cur_fov ^ 1] : nullptr, 2, S(stream));
+}
 
 int agx_fovea_fixed(agx_ctx *ctx, const void *d_action, int action_dtype, const uint8_t *d_mask, float *d_obs,
                     int32_t *d_fov_loc, void *stream) {
@@ -1059,12 +1141,13 @@ int agx_fovea_fixed(agx_ctx *ctx, const void *d_action, int action_dtype, const 
     int rc = check_dt(ctx, d_action, action_dtype);
     if (rc) return rc;
     DeviceGuard g(c.device);
-    const FovParams p = fov_params(ctx, d_action, action_dtype, nullptr, d_mask, d_obs, d_fov_loc, nullptr);
+    FovParams p = fov_params(ctx, d_action, action_dtype, nullptr, d_mask, d_obs, d_fov_loc, nullptr);
+    fov_range(ctx, p);
     const size_t lds = fixed_lds(c);
     const bool headline = c.obs_h == 84 && c.obs_w == 84 && c.fov_h == 30 && c.fov_w == 30;
     using GS = GeomS<84, 84, 30, 30>;
     const GeomR gr{c.obs_h, c.obs_w, c.fov_h, c.fov_w};
-    const dim3 grid(c.frame_stack * ctx->planes, c.num_envs), block(kThreads);
+    const dim3 grid(c.frame_stack * ctx->planes, ctx->rng_n), block(kThreads);
 #define LAUNCH(MODE)                                                                                     \
     do {                                                                                                 \
         if (headline)                                                                                    \
@@ -1077,7 +1160,7 @@ int agx_fovea_fixed(agx_ctx *ctx, const void *d_action, int action_dtype, const 
     // with the one-slot form at N=1024 (26.3 vs 25.8 us) - the launch is store-limited
     if (c.out_mode == AGX_OUT_RESIZE && c.frame_stack % 2 == 0 && ctx->tune.pair == 1 && ctx->obs_type == AGX_OBS_F32 &&
         ctx->planes == 1) {
-        const dim3 grid2(c.frame_stack / 2, c.num_envs);
+        const dim3 grid2(c.frame_stack / 2, ctx->rng_n);
         if (headline)
             hipLaunchKernelGGL((k_fovea_fixed2<GS>), grid2, block, fixed2_lds(c), S(stream), GS{}, p);
         else
@@ -1097,6 +1180,7 @@ int agx_fovea_fixed(agx_ctx *ctx, const void *d_action, int action_dtype, const 
         });
         });
 #undef LAUNCH
+    fov_carry(ctx, stream);
     AGX_HIP(ctx, hipGetLastError());
     ctx->cur_fov ^= 1;
     return AGX_OK;
@@ -1109,6 +1193,7 @@ int agx_step_fixed(agx_ctx *ctx, const uint8_t *d_frames, const uint8_t *d_cmd, 
     const agx_config &c = ctx->cfg;
     if (ctx->planes != 1) return refuse_rgb(ctx, "agx_step_fixed");
     if (c.kind != AGX_KIND_FIXED) return fail(ctx, AGX_E_STATE, "agx_step_fixed on a context of kind %d", c.kind);
+    if (!full_range(ctx)) return refuse_range(ctx, "agx_step_fixed");
     if (!d_frames || !d_cmd || !d_obs) return fail(ctx, AGX_E_INVALID, "agx_step_fixed: null buffer");
     int rc = check_dt(ctx, d_action, action_dtype);
     if (rc) return rc;
@@ -1280,7 +1365,9 @@ int agx_fovea_peripheral(agx_ctx *ctx, const void *d_action, int action_dtype, c
     int rc = check_dt(ctx, d_action, action_dtype);
     if (rc) return rc;
     DeviceGuard g(c.device);
-    const FovParams p = fov_params(ctx, d_action, action_dtype, nullptr, d_mask, d_obs, d_fov_loc, nullptr);
+    FovParams p = fov_params(ctx, d_action, action_dtype, nullptr, d_mask, d_obs, d_fov_loc, nullptr);
+    fov_range(ctx, p);
+    const int en = ctx->rng_n;             // envs of the launch
     const GeomR gr{c.obs_h, c.obs_w, c.fov_h, c.fov_w};
     const bool generic_only = ctx->tune.generic != 0;                               // tuning / testing knob
     const int planes = c.frame_stack * ctx->planes;                                  // workgroups per env
@@ -1289,7 +1376,7 @@ int agx_fovea_peripheral(agx_ctx *ctx, const void *d_action, int action_dtype, c
     return with_obs_type(ctx->obs_type, [&](auto tag) {
     using OT = decltype(tag);
     if (!generic_only && ctx->p3_mt && ctx->tune.per_v2 == 0) {
-        const dim3 grid(planes, c.num_envs), block(kThreads);
+        const dim3 grid(planes, en), block(kThreads);
         const size_t lds = ctx->p3_lds;
         using GS = PGeomS<84, 84, 30, 30, 20, 20>;
         const PGeomR pg{c.obs_h, c.obs_w, c.fov_h, c.fov_w, c.per_h, c.per_w};
@@ -1313,7 +1400,7 @@ int agx_fovea_peripheral(agx_ctx *ctx, const void *d_action, int action_dtype, c
         g.oh = c.obs_h; g.ow = c.obs_w; g.fh = c.fov_h; g.fw = c.fov_w; g.ph = c.per_h; g.pw = c.per_w;
         g.same = (c.per_h == c.obs_h && c.per_w == c.obs_w) ? 1 : 0;                // torchvision returns the input
         const int mt = std::max(ctx->per_maxt[0], ctx->per_maxt[1]);
-        const dim3 grid(planes, c.num_envs), block(kThreads);
+        const dim3 grid(planes, en), block(kThreads);
         const size_t lds = per2_lds(c);
         // both squeeze tables are padded to their own bucket; the kernel bound must not exceed either row pitch
         const bool same_bucket = ctx->per_maxt[0] == ctx->per_maxt[1];
@@ -1324,12 +1411,13 @@ int agx_fovea_peripheral(agx_ctx *ctx, const void *d_action, int action_dtype, c
         else if (same_bucket && mt == 16) AGX_LAUNCH(1, (k_fovea_peripheral2<16, OT, NC>), grid, block, lds, S(stream), g, p);
         else AGX_LAUNCH(1, (k_fovea_peripheral2<0, OT, NC>), grid, block, lds, S(stream), g, p);
     } else {
-        hipLaunchKernelGGL((k_fovea_generic<AGX_KIND_PERIPHERAL, OT, NC>), dim3(planes, c.num_envs), dim3(kThreads),
+        hipLaunchKernelGGL((k_fovea_generic<AGX_KIND_PERIPHERAL, OT, NC>), dim3(planes, en), dim3(kThreads),
                            generic_lds(c), S(stream), gr, p);
     }
     return 0;
     });
     });
+    fov_carry(ctx, stream);
     AGX_HIP(ctx, hipGetLastError());
     ctx->cur_fov ^= 1;
     return AGX_OK;
@@ -1344,7 +1432,9 @@ int agx_fovea_flexible(agx_ctx *ctx, const void *d_action, int action_dtype, con
     int rc = check_dt(ctx, d_action, action_dtype);
     if (rc) return rc;
     DeviceGuard g(c.device);
-    const FovParams p = fov_params(ctx, d_action, action_dtype, d_action_type, d_mask, d_obs, d_fov_loc, d_fov_res);
+    FovParams p = fov_params(ctx, d_action, action_dtype, d_action_type, d_mask, d_obs, d_fov_loc, d_fov_res);
+    fov_range(ctx, p);
+    const int en = ctx->rng_n;             // envs of the launch
     const GeomR gr{c.obs_h, c.obs_w, c.fov_h, c.fov_w};
     const bool generic_only = ctx->tune.generic != 0;                               // tuning / testing knob
     const size_t lds2 = flex2_lds(c, ctx->flex_tab_floats);
@@ -1355,14 +1445,14 @@ int agx_fovea_flexible(agx_ctx *ctx, const void *d_action, int action_dtype, con
     using OT = decltype(tag);
     if (!generic_only && ctx->f3_ok && ctx->tune.flex_v2 == 0) {
         const size_t lds3 = (size_t)ctx->f3.r0_bytes + ctx->f3.r1_bytes + (size_t)c.obs_h * sizeof(int4);
-        const dim3 grid(planes, c.num_envs), block(kThreads);
+        const dim3 grid(planes, en), block(kThreads);
         using GS = GeomS<84, 84, 30, 30>;
         if (c.obs_h == 84 && c.obs_w == 84 && c.fov_h == 30 && c.fov_w == 30)
             AGX_LAUNCH(1, (k_fovea_flexible3<GS, OT, NC>), grid, block, lds3, S(stream), GS{}, ctx->f3, p);
         else
             AGX_LAUNCH(1, (k_fovea_flexible3<GeomR, OT, NC>), grid, block, lds3, S(stream), gr, ctx->f3, p);
     } else if (!generic_only && ctx->fr_ok && ctx->tune.flex_v2 == 0 && c.out_mode != AGX_OUT_RESIZE) {
-        const dim3 grid(planes, c.num_envs), block(kThreads);
+        const dim3 grid(planes, en), block(kThreads);
         using GS = GeomS<84, 84, 30, 30>;
         const bool headline = c.obs_h == 84 && c.obs_w == 84 && c.fov_h == 30 && c.fov_w == 30;
         if (c.out_mode == AGX_OUT_MASK) {
@@ -1381,15 +1471,16 @@ int agx_fovea_flexible(agx_ctx *ctx, const void *d_action, int action_dtype, con
             fam[k]->meta = ctx->flex_meta[k];
         }
         g.oh = c.obs_h; g.ow = c.obs_w; g.fh = c.fov_h; g.fw = c.fov_w;
-        if (c.out_mode == AGX_OUT_RESIZE) AGX_LAUNCH(1, (k_fovea_flexible2<true, OT, NC>), dim3(planes, c.num_envs), dim3(kThreads), lds2, S(stream), g, p);
-        else AGX_LAUNCH(1, (k_fovea_flexible2<false, OT, NC>), dim3(planes, c.num_envs), dim3(kThreads), lds2, S(stream), g, p);
+        if (c.out_mode == AGX_OUT_RESIZE) AGX_LAUNCH(1, (k_fovea_flexible2<true, OT, NC>), dim3(planes, en), dim3(kThreads), lds2, S(stream), g, p);
+        else AGX_LAUNCH(1, (k_fovea_flexible2<false, OT, NC>), dim3(planes, en), dim3(kThreads), lds2, S(stream), g, p);
     } else {
-        hipLaunchKernelGGL((k_fovea_generic<AGX_KIND_FLEXIBLE, OT, NC>), dim3(planes, c.num_envs), dim3(kThreads),
+        hipLaunchKernelGGL((k_fovea_generic<AGX_KIND_FLEXIBLE, OT, NC>), dim3(planes, en), dim3(kThreads),
                            generic_lds(c), S(stream), gr, p);
     }
     return 0;
     });
     });
+    fov_carry(ctx, stream);
     AGX_HIP(ctx, hipGetLastError());
     ctx->cur_fov ^= 1;
     return AGX_OK;
@@ -1446,6 +1537,7 @@ int agx_fovea_flexible_packed(agx_ctx *ctx, const void *d_action, int action_dty
     if (!ctx) return AGX_E_INVALID;
     const agx_config &c = ctx->cfg;
     if (ctx->planes != 1) return refuse_rgb(ctx, "agx_fovea_flexible_packed");
+    if (!full_range(ctx)) return refuse_range(ctx, "agx_fovea_flexible_packed");
     if (c.kind != AGX_KIND_FLEXIBLE || c.out_mode != AGX_OUT_RAW)
         return fail(ctx, AGX_E_STATE, "agx_fovea_flexible_packed needs a flexible context in raw-crop mode (kind %d, out_mode %d)",
                     c.kind, c.out_mode);
@@ -1500,6 +1592,7 @@ int agx_step_flexible_packed(agx_ctx *ctx, const uint8_t *d_screens, int screens
     if (!ctx) return AGX_E_INVALID;
     const agx_config &c = ctx->cfg;
     if (ctx->planes != 1) return refuse_rgb(ctx, "agx_step_flexible_packed");
+    if (!full_range(ctx)) return refuse_range(ctx, "agx_step_flexible_packed");
     if (c.kind != AGX_KIND_FLEXIBLE || c.out_mode != AGX_OUT_RAW)
         return fail(ctx, AGX_E_STATE, "agx_step_flexible_packed needs a flexible context in raw-crop mode (kind %d, out_mode %d)",
                     c.kind, c.out_mode);
@@ -1557,3 +1650,4 @@ int agx_step_flexible_packed(agx_ctx *ctx, const uint8_t *d_screens, int screens
 }  // extern "C"
 
 #include "agx_loop_impl.h"
+#include "agx_hostout_impl.h"

@@ -40,8 +40,12 @@ __global__ __launch_bounds__(kThreads) void k_gather_int2(const int2 *src, const
 
 }  // namespace agx
 
+struct agx_hostout;                   // agx_loop_step_host's streams, events and pinned side buffers (agx_hostout_impl.h)
+static void hostout_free(agx_hostout *h);
+
 struct agx_loop {
     agx_ctx *ctx = nullptr;
+    agx_hostout *ho = nullptr;        // made by the first agx_loop_step_host
     agx_host_source src{};
     agx_loop_config cfg{};
     int N = 0;
@@ -198,6 +202,7 @@ int agx_loop_destroy(agx_loop *l) {
     if (!l) return AGX_OK;
     DeviceGuard g(l->ctx->cfg.device);
     (void)hipDeviceSynchronize();                      // copies from the pinned sets may still be in flight
+    if (l->ho) hostout_free(l->ho);
     for (int b = 0; b < 2; ++b) {
         if (l->h_frames[b]) (void)hipHostFree(l->h_frames[b]);
         if (l->h_cmd[b]) (void)hipHostFree(l->h_cmd[b]);
