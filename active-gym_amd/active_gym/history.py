@@ -1,0 +1,178 @@
+"""FrameHistory — ctypes view of include/agx_history.h: an on-device history of the u8 frames and fov_loc behind every
+observation, and the kernel that re-creates the observation of any retained env-step.
+
+An observation is ``[fs][h][w]`` elements (113 KB per env-step at float32 84 x 84 x 4): too large to keep.  It is a pure
+function of the env's last ``fs`` u8 frames (7 KB each, one new one per env-step) and its fov_loc (8 bytes); the history
+keeps those, ``capacity`` env-steps per env, in HBM::
+
+    hist = FrameHistory(pipe, capacity=100_000)           # hist.nbytes: about capacity * N * (obs_h * obs_w + 9) bytes
+    pipe.ingest(frames, cmd); obs, loc = pipe.fovea(action)
+    index = hist.push(cmd)                                  # i64 [N]: store (env, index) in the replay buffer, not obs
+    ...
+    obs, loc, valid = hist.observe(env, index)              # bit for bit what the step returned, where still retained
+    obs, loc, valid = hist.observe(env, index, action=a)    # ... had the env looked at `a` (absolute) instead
+
+The entry points live in libagx.so, in a header and a binding of their own (active_gym/_native.py is unchanged)."""
+from __future__ import annotations
+
+import ctypes as C
+from typing import Optional
+
+import torch
+
+from . import _native as nat
+
+_P = C.c_void_p
+HIST_FOVEA, HIST_FULL = 0, 1          # AGX_HIST_*
+_WHAT = {"fovea": HIST_FOVEA, "full": HIST_FULL}
+
+SIGNATURES = {
+    "agx_history_create": (C.c_int, [_P, C.c_int32, C.POINTER(_P)]),
+    "agx_history_destroy": (C.c_int, [_P]),
+    "agx_history_clear": (C.c_int, [_P, _P]),
+    "agx_history_bytes": (C.c_int64, [_P]),
+    "agx_history_push": (C.c_int, [_P, _P, _P, _P]),
+    "agx_history_last_index": (C.c_int, [_P, _P, _P]),
+    "agx_history_observe": (C.c_int, [_P, C.c_int, _P, _P, C.c_int32, _P, C.c_int, _P, _P, _P, _P]),
+    "agx_loop_set_history": (C.c_int, [_P, _P]),
+}
+_bound = False
+
+
+def lib():
+    global _bound
+    handle = nat.lib()
+    if not _bound:
+        for name, (res, args) in SIGNATURES.items():
+            fn = getattr(handle, name)           # AttributeError if the .so does not export it
+            fn.restype, fn.argtypes = res, args
+        _bound = True
+    return handle
+
+
+def check_env_history(kind: str, history_len, channels: int = 1, ragged_obs: str = "padded") -> int:
+    """``args.history_len`` of a vector env -> T (0: no history); ValueError, before any GPU work, for what the history does
+    not serve: kinds other than base / fixed, colour frames, packed ragged observations."""
+    t = int(history_len or 0)
+    if t < 0:
+        raise ValueError(f"history_len must be >= 0, got {t}")
+    if t > 0:
+        if kind not in ("base", "fixed"):
+            raise ValueError(f"history_len > 0 needs kind 'base' or 'fixed', got {kind!r} (peripheral / flexible re-observation is not built)")
+        if int(channels) != 1:
+            raise ValueError("history_len > 0 needs gray frames (colour re-observation is not built)")
+        if ragged_obs == "packed":
+            raise ValueError("history_len > 0 with ragged_obs='packed': packed ragged crops are not re-observed")
+    return t
+
+
+class FrameHistory:
+    def __init__(self, pipe, capacity: int):
+        """pipe: an ObsPipeline of kind "base" or "fixed" with gray frames; capacity: env-steps kept per env (>= frame_stack).
+        Create it before the pipeline's first ingest (a new history takes the frames before an env's first append to be zero,
+        which is what a new pipeline's stack holds), or start every env with a CMD_CLEAR ingest as a reset does."""
+        self._lib = lib()
+        self.pipe = pipe
+        self.device = pipe.device
+        self.capacity = int(capacity)
+        self.num_envs = pipe.num_envs
+        self._h = _P()
+        nat.check(self._lib.agx_history_create(pipe._ctx, self.capacity, C.byref(self._h)), pipe._ctx)
+        # the history holds the context's raw handle: it goes before the pipeline does
+        if not hasattr(pipe, "_dependents"):
+            pipe._dependents = []
+        pipe._dependents.append(self)
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h.value:
+            self._lib.agx_history_destroy(self._h)
+            self._h = _P()
+            if self in getattr(self.pipe, "_dependents", ()):
+                self.pipe._dependents.remove(self)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001
+            pass
+
+    @property
+    def handle(self):
+        """The agx_history* (for agx_loop_set_history)."""
+        return self._h
+
+    @property
+    def nbytes(self) -> int:
+        return int(self._lib.agx_history_bytes(self._h))
+
+    def _chk(self, t, shape, dtype, name):
+        return self.pipe._chk(t, shape, dtype, name)
+
+    def _check(self, rc):
+        nat.check(rc, self.pipe._ctx)
+
+    def clear(self):
+        """Every index becomes invalid, the per-env indices restart at 0."""
+        self._check(self._lib.agx_history_clear(self._h, self.pipe._stream()))
+
+    def push(self, cmd: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """After one ingest(.., cmd) and its observation: append each env's newest frame and current fov_loc.  Returns the i64 [N]
+        index of the append (-1 for an env whose command byte carries CMD_SKIP).  One push per ingest."""
+        n = self.num_envs
+        pc = self._chk(cmd, (n,), torch.uint8, "cmd")
+        if out is None:
+            out = torch.empty((n,), dtype=torch.int64, device=self.device)
+        po = self._chk(out, (n,), torch.int64, "out")
+        self._check(self._lib.agx_history_push(self._h, pc, po, self.pipe._stream()))
+        return out
+
+    def last_index(self, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """i64 [N]: the index of each env's newest append (-1: none yet)."""
+        n = self.num_envs
+        if out is None:
+            out = torch.empty((n,), dtype=torch.int64, device=self.device)
+        po = self._chk(out, (n,), torch.int64, "out")
+        self._check(self._lib.agx_history_last_index(self._h, po, self.pipe._stream()))
+        return out
+
+    def obs_row_shape(self, what: str = "fovea"):
+        """Shape of one re-created observation: the pipeline's own row, or (fs, obs_h, obs_w) for what="full"."""
+        return tuple(self.pipe.full_shape[1:] if what == "full" else self.pipe.obs_shape[1:])
+
+    def observe(self, env: torch.Tensor, index: torch.Tensor, action: Optional[torch.Tensor] = None, what: str = "fovea",
+                out: Optional[torch.Tensor] = None, loc_out: Optional[torch.Tensor] = None, valid_out: Optional[torch.Tensor] = None):
+        """Re-create the observations of the samples (env[b], index[b]) - i32 [B], i64 [B]; any order, repeats allowed.
+        action: None (the recorded fov_loc: bit for bit the step's observation) or [B, 2] f32 / f64 / i32 / i64, an ABSOLUTE
+        sensory action to look at instead.  what: "fovea" (the pipeline's own observation) or "full" (the stack, k/255).
+        Returns (obs [B, ...], fov_loc i32 [B, 2], valid u8 [B]); rows of invalid samples (never issued, or evicted) are left as
+        they were in `out` / `loc_out` (uninitialised when this call allocated them).  fov_loc is not written by a base pipeline."""
+        from .pipeline import _DT
+        if what not in _WHAT:
+            raise ValueError(f"what must be 'fovea' or 'full', got {what!r}")
+        if not isinstance(env, torch.Tensor) or env.dim() != 1:
+            raise ValueError("env must be a 1-D int32 tensor")
+        b = int(env.shape[0])
+        pe = self._chk(env, (b,), torch.int32, "env")
+        pi = self._chk(index, (b,), torch.int64, "index")
+        pa, dt = None, 0
+        if action is not None:
+            if action.dtype not in _DT:
+                raise TypeError(f"sensory action dtype {action.dtype} not supported (f32/f64/i32/i64)")
+            pa = self._chk(action, (b, 2), None, "action")
+            dt = _DT[action.dtype]
+        shape = (b,) + self.obs_row_shape(what)
+        if out is None:
+            out = torch.empty(shape, dtype=self.pipe.obs_dtype, device=self.device)
+        po = self._chk(out, shape, self.pipe.obs_dtype, "out")
+        if loc_out is None:
+            loc_out = torch.empty((b, 2), dtype=torch.int32, device=self.device)
+        pl = self._chk(loc_out, (b, 2), torch.int32, "loc_out")
+        if valid_out is None:
+            valid_out = torch.empty((b,), dtype=torch.uint8, device=self.device)
+        pv = self._chk(valid_out, (b,), torch.uint8, "valid_out")
+        self._check(self._lib.agx_history_observe(self._h, _WHAT[what], pe, pi, b, pa, dt, po, pl, pv, self.pipe._stream()))
+        return out, loc_out, valid_out
+
+    def attach(self, loop):
+        """The native step loop pushes from now on (agx_loop_set_history); ``loop``: a NativeStepLoop of the same pipeline."""
+        loop.check(self._lib.agx_loop_set_history(loop.handle, self._h))

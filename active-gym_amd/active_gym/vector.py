@@ -109,12 +109,18 @@ class AtariVecEnv:
     the reference; a cuda device -> torch tensors that stay in HBM), ``antialias``, ``num_workers``,
     ``host_obs_chunks`` (C > 0 with ``device=None`` and a native frame source: step() runs in the native loop and
     brings the observations home in C env chunks, each chunk's device-to-host copy under the next chunk's
-    host-to-device copy and kernels; ``env.host_obs_chunks`` is the value in effect, 0 = the unchunked path)."""
+    host-to-device copy and kernels; ``env.host_obs_chunks`` is the value in effect, 0 = the unchunked path),
+    ``history_len`` (T > 0, kinds base / fixed: the env owns a :class:`~active_gym.history.FrameHistory` of T env-steps per
+    env as ``env.history``, pushes after every observation it returns - in the Python loop and in the native loop - and
+    ``info["history_index"]`` is the index of the observation ``step`` / ``reset`` returned; for an env that was autoreset in
+    this step the terminal observation is ``index - 1``.  0, the default: no history, no key)."""
 
     _loop = None             # NativeStepLoop when the native step loop drives this env (subclasses with their own source: never)
     _want_loop = False
     host_obs_chunks = 0      # chunks of the host-output step in effect (args.host_obs_chunks where its conditions hold, else 0)
     _host_step = None        # native_hostout.HostOutStep when host_obs_chunks > 0
+    history = None           # history.FrameHistory when args.history_len > 0
+    history_len = 0
 
     def __init__(self, args, num_envs: int, kind: str = "fixed", env_offset: int = 0, noop_fn=None,
                  autoreset: bool = True, noop_per_env: bool = False):
@@ -123,6 +129,8 @@ class AtariVecEnv:
         if kind not in _KINDS:
             raise ValueError(f"kind must be one of {_KINDS}")
         self.obs_dtype = _resolve_env_obs_dtype(args)
+        from .history import check_env_history
+        self.history_len = check_env_history(kind, getattr(args, "history_len", 0), 1, getattr(args, "ragged_obs", "padded"))
         if not torch.cuda.is_available():
             raise RuntimeError("active_gym envs need a ROCm GPU: the observation pipeline has no CPU implementation")
         self.args = args
@@ -164,6 +172,8 @@ class AtariVecEnv:
 
     def _build_pipeline(self):
         args, kind = self.args, self.kind
+        from .history import FrameHistory, check_env_history
+        check_env_history(kind, self.history_len, self.channels, getattr(args, "ragged_obs", "padded"))
         kw = dict(num_envs=self.num_envs, kind=kind, obs_size=self.obs_size, frame_stack=self.frame_stack,
                   device=self.device, obs_dtype=self.obs_dtype, channels=self.channels)
         if kind != "base":
@@ -190,6 +200,7 @@ class AtariVecEnv:
                 mask_out, resize_to_full = False, True                                  # fov_env.py:361-362
             self.mask_out, self.resize_to_full = mask_out, resize_to_full
         self.pipe = ObsPipeline(**kw)
+        self.history = FrameHistory(self.pipe, self.history_len) if self.history_len > 0 else None
 
     def _build_spaces(self):
         kind = self.kind
@@ -334,6 +345,8 @@ class AtariVecEnv:
             # its pinned staging is allocated inside: bound to this rank's CPUs (first touch on the GPU's NUMA node)
             with hostplan.bound_to(self.host_plan["cpus"] and self.host_plan["domain"]):
                 self._loop = NativeStepLoop(self.pipe, self.runner, gray=self._gray, compact=self._compact, autoreset=self.autoreset)
+                if self.history is not None:
+                    self.history.attach(self._loop)          # the loop pushes after every observation it writes
                 self._host_step = None
                 if self.host_obs_chunks > 0:
                     from .native_hostout import HostOutStep
@@ -532,6 +545,15 @@ class AtariVecEnv:
     def _out(self, t: torch.Tensor):
         return t.cpu().numpy() if self._numpy_out else t
 
+    def _hist_push(self, cmd):
+        """Python loop: append to the frame history after an ingest(cmd) + observation (the native loop pushes itself)."""
+        if self.history is not None:
+            self.history.push(cmd)
+
+    def _hist_index(self):
+        """i64 [N]: the history index of each env's newest observation (NumPy with host outputs)."""
+        return self._out(self.history.last_index())
+
     def _next_stage(self):
         st = getattr(self, "_stage", None)
         if st is not None and len(st) > 1:
@@ -601,6 +623,8 @@ class AtariVecEnv:
                 info["fov_loc"] = self._loc.to(torch.int64)
                 if self.kind == "flexible":
                     info["fov_res"] = self._res.to(torch.int64)
+        if self.history is not None:
+            info["history_index"] = self._hist_index()
         return self._extra_info(info)
 
     @staticmethod
@@ -638,6 +662,7 @@ class AtariVecEnv:
         # next) must not be overwritten by the reset observation
         self._next_obs_buffer()
         obs = self._observe()
+        self._hist_push(self._d_cmd)
         self._release_dset()
         self._was_reset = True
         return self._ret_obs(obs), self._with_masks(self._info(np.zeros(self.num_envs)), self.num_envs)
@@ -684,6 +709,7 @@ class AtariVecEnv:
         else:
             self._ingest()
             obs = self._observe(sens, stype)
+            self._hist_push(self._d_cmd)
         self.ep_len += 1
         self.cumulative_reward += raw                   # unclipped, fov_env.py:62
         info = self._info(raw)
@@ -717,6 +743,7 @@ class AtariVecEnv:
             else:
                 self.pipe.fovea_reset(mask)
                 self._observe(None, None, mask=mask)
+            self._hist_push(self._d_rcmd)
             rinfo = self._info(np.zeros(n))
             for key in info:
                 if isinstance(info[key], torch.Tensor):
@@ -762,6 +789,7 @@ class AtariVecEnv:
         info = {"raw_reward": raw.copy(), "reward": self.cumulative_reward.copy(), "ep_len": self.ep_len.copy()}
         k = len(idx)
         final = None
+        hist_idx = self._hist_index() if self.history is not None else None      # after the loop's step and reset pushes
         if self.autoreset and k:
             # terminal observations / infos of the envs that ended an episode: rows of the loop's side buffers (cloned: the loop
             # reuses them next step), handed out as views like the Python loop's index_select rows
@@ -784,6 +812,8 @@ class AtariVecEnv:
                 fi = {key: (val[i].copy() if isinstance(val[i], np.ndarray) else val[i]) for key, val in info.items()}
                 for key, val in gathered.items():
                     fi[key] = val[j]
+                if hist_idx is not None:
+                    fi["history_index"] = hist_idx[i] - 1       # the terminal observation: the append before the reset's
                 final_info[i] = fi
             final = (final_obs, final_info)
             self.cumulative_reward[idx] = 0
@@ -802,6 +832,8 @@ class AtariVecEnv:
                 info["fov_loc"] = self._loc.to(torch.int64)
                 if self.kind == "flexible":
                     info["fov_res"] = self._res.to(torch.int64)
+        if hist_idx is not None:
+            info["history_index"] = hist_idx
         infos = self._with_masks(self._extra_info(info), n)
         if final is not None:
             infos["final_observation"] = final[0]
@@ -842,6 +874,7 @@ class AtariVecEnv:
         else:
             self.pipe.fovea_reset(mask)
             obs = self._observe(None, None, mask=mask)
+        self._hist_push(self._d_rcmd)
         self._release_dset()
         self._was_reset = True
         return self._ret_obs(obs), self._with_masks(self._info(np.zeros(n)), n)

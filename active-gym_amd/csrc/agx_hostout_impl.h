@@ -190,6 +190,7 @@ int agx_loop_step_host(agx_loop *l, const int32_t *motor, const void *d_action, 
                                            hipMemcpyDeviceToHost, h->d2h));
         }
     }   // ---- 3. the whole batch again
+    if (l->hist) LOOP_AGX(l, agx_history_push(l->hist, l->d_cmd[ds], nullptr, st));      // (include/agx_history.h: whole-batch, behind the last chunk)
     l->done_idx.clear();
     for (int i = 0; i < N; ++i)
         if (l->done[i]) l->done_idx.push_back(i);

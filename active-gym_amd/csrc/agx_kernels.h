@@ -8,6 +8,7 @@
 //   k_stack_u8 / k_full K0  ring -> stack order (u8 / f32 k/255)
 //   k_fovea_fixed       K2  clip/rint sensory action, crop, {raw | mask-out | bilinear upsample}
 //   k_fovea_generic     K3/K4 peripheral squeeze-expand + paste, flexible (ragged) fovea
+//   k_history_push / k_history_observe  K5  frame history: append the newest ring frame / re-create a retained observation
 //
 // Persistent per-env state (owned by the context, see agx_api.hip):
 //   ring  u8 [N][fs][oh][ow]   numerators k of the reference's float32 k/255 frames
@@ -20,6 +21,7 @@
 #include "agx_k1_ingest.h"
 #include "agx_fov_common.h"
 #include "agx_k2_fixed.h"
+#include "agx_k5_history.h"
 #include "agx_k34_resample.h"
 #include "agx_k3_per3.h"
 #include "agx_k4_flex3.h"

@@ -2,6 +2,7 @@
 // the public entry points of this very library, plus two row-copy kernels and the HIP runtime's copy / event calls).
 #pragma once
 #include "agx_loop.h"
+#include "agx_history.h"
 
 namespace agx {
 
@@ -46,6 +47,7 @@ static void hostout_free(agx_hostout *h);
 struct agx_loop {
     agx_ctx *ctx = nullptr;
     agx_hostout *ho = nullptr;        // made by the first agx_loop_step_host
+    agx_history *hist = nullptr;      // agx_loop_set_history (include/agx_history.h): pushed after every observation
     agx_host_source src{};
     agx_loop_config cfg{};
     int N = 0;
@@ -188,6 +190,8 @@ int loop_reset_subset(agx_loop *l, int k, float *d_obs, int32_t *d_loc, int32_t 
     } else {
         LOOP_AGX(l, loop_observe(l, nullptr, 0, nullptr, nullptr, d_obs, nullptr, nullptr, st));
     }
+    // the frame history: the reset envs append (CLEAR), the others are skipped - this pass's own command bytes
+    if (l->hist) LOOP_AGX(l, agx_history_push(l->hist, rmeta_cmd(l->d_rmeta, N), nullptr, st));
     LOOP_HIP(l, hipEventRecord(l->ev_rfree, st));
     return AGX_OK;
 }
@@ -360,6 +364,7 @@ int agx_loop_step(agx_loop *l, const int32_t *motor, const void *d_action, int a
     h2d += (int64_t)N + (int64_t)N * (int64_t)env_bytes;
     LOOP_AGX(l, loop_ingest(l, l->d_frames[ds], l->d_cmd[ds], st));
     LOOP_AGX(l, loop_observe(l, l->fovea ? d_action : nullptr, action_dtype, d_action_type, nullptr, d_obs, d_fov_loc, d_fov_res, st));
+    if (l->hist) LOOP_AGX(l, agx_history_push(l->hist, l->d_cmd[ds], nullptr, st));
     l->done_idx.clear();
     for (int i = 0; i < N; ++i)
         if (l->done[i]) l->done_idx.push_back(i);
