@@ -121,6 +121,7 @@ class AtariVecEnv:
     _host_step = None        # native_hostout.HostOutStep when host_obs_chunks > 0
     history = None           # history.FrameHistory when args.history_len > 0
     history_len = 0
+    _glimpse_of = None       # the history the cached glimpse.GlimpseMemory objects (by glimpses) read
 
     def __init__(self, args, num_envs: int, kind: str = "fixed", env_offset: int = 0, noop_fn=None,
                  autoreset: bool = True, noop_per_env: bool = False):
@@ -553,6 +554,23 @@ class AtariVecEnv:
     def _hist_index(self):
         """i64 [N]: the history index of each env's newest observation (NumPy with host outputs)."""
         return self._out(self.history.last_index())
+
+    def glimpse_memory(self, glimpses: int = 3, out: Optional[torch.Tensor] = None):
+        """The glimpse memory of the observation the last ``reset`` / ``step`` returned, for all N envs: the elementwise
+        maximum over each env's last up-to-``glimpses`` observations since its last reset (glimpse.GlimpseMemory.observe at
+        ``history.last_index()``; an env autoreset in the last step gives just its returned observation).  Needs
+        ``history_len`` > 0, kind "fixed" and mask_out or resize_to_full mode: ValueError otherwise."""
+        from .glimpse import GlimpseMemory
+        if self.history is None:
+            raise ValueError("glimpse_memory needs a frame history (AtariEnvArgs.history_len > 0)")
+        if self._glimpse_of is not self.history:                # a rebuilt pipeline (rekind) has a new history
+            self._glimpse_of, self._glimpse = self.history, {}
+            self._glimpse_env = torch.arange(self.num_envs, dtype=torch.int32, device=self.device)
+        mem = self._glimpse.get(int(glimpses))
+        if mem is None:
+            mem = self._glimpse[int(glimpses)] = GlimpseMemory(self.history, glimpses)      # ValueError for a kind or mode that is not served
+        obs, _, _ = mem.observe(self._glimpse_env, self.history.last_index(), out=out)
+        return self._out(obs)
 
     def _next_stage(self):
         st = getattr(self, "_stage", None)

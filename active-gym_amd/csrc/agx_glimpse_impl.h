@@ -1,0 +1,86 @@
+// agx_glimpse_impl.h - the glimpse memory declared in include/agx_glimpse.h (included at the end of agx_api.hip, behind the
+// frame history it reads): the checks and the launches of k_history_memory (agx_k6_glimpse.h).
+#pragma once
+#include "agx_glimpse.h"
+
+namespace {
+
+// the LDS carve of k_history_memory
+size_t memory_lds(const agx_config &c, int glimpses, bool headline) {
+    const size_t raw = ((size_t)c.fov_h * c.obs_w + 15) & ~(size_t)15;
+    size_t b = agx::kMemTableBytes + (size_t)glimpses * raw;
+    if (c.out_mode == AGX_OUT_RESIZE) {
+        b += (size_t)c.obs_h * sizeof(Tap) + 2 * (size_t)c.fov_h * c.obs_w * sizeof(float);
+        if (!headline) b += (size_t)c.obs_h * c.obs_w * sizeof(float);      // the running maximum of the run-time geometry form
+    }
+    return b;
+}
+
+}  // namespace
+
+extern "C" {
+
+int agx_history_observe_memory(agx_history *h, int32_t glimpses, const int32_t *d_env, const int64_t *d_index, int32_t B, float *d_obs,
+                               int32_t *d_fov_loc, uint8_t *d_taken, void *stream) {
+    if (!h) return AGX_E_INVALID;
+    agx_ctx *ctx = h->ctx;
+    const agx_config &c = ctx->cfg;
+    if (glimpses < 1 || glimpses > AGX_GLIMPSE_LIMIT)
+        return fail(ctx, AGX_E_INVALID, "agx_history_observe_memory: glimpses must be 1 .. %d, got %d", AGX_GLIMPSE_LIMIT, glimpses);
+    if (B < 0) return fail(ctx, AGX_E_INVALID, "agx_history_observe_memory: B = %d", B);
+    if (c.kind != AGX_KIND_FIXED)
+        return fail(ctx, AGX_E_STATE, "agx_history_observe_memory: a context without a fovea has no glimpses (AGX_KIND_FIXED only)");
+    if (c.out_mode == AGX_OUT_RAW)
+        return fail(ctx, AGX_E_STATE, "agx_history_observe_memory: raw-crop mode is not served (a maximum over crops at different positions means nothing; mask-out and resize_to_full are)");
+    if (!full_range(ctx)) return hist_refuse_range(h, "agx_history_observe_memory");
+    const bool headline = c.obs_h == 84 && c.obs_w == 84 && c.fov_h == 30 && c.fov_w == 30;
+    const size_t lds = memory_lds(c, glimpses, headline);
+    if (lds > kMaxLds)
+        return fail(ctx, AGX_E_STATE, "agx_history_observe_memory: %d glimpses of this geometry need %zu B of LDS per workgroup (limit %zu)", glimpses, lds,
+                    kMaxLds);
+    if (B == 0) return AGX_OK;
+    if (!d_env || !d_index || !d_obs) return fail(ctx, AGX_E_INVALID, "agx_history_observe_memory: null buffer");
+    DeviceGuard g(c.device);
+    FovParams p = fov_params(ctx, nullptr, 0, nullptr, nullptr, d_obs, nullptr, nullptr);
+    p.relative = 0;
+    p.ring = nullptr;
+    p.head = nullptr;
+    p.loc_in = p.loc_out = nullptr;
+    agx::HistMemParams q;
+    q.h = h->p;
+    q.glimpses = glimpses;
+    using GS = GeomS<84, 84, 30, 30>;
+    const GeomR gr{c.obs_h, c.obs_w, c.fov_h, c.fov_w};
+    const size_t row_bytes = (size_t)c.frame_stack * (size_t)c.obs_h * c.obs_w * obs_elem_bytes(ctx->obs_type);
+    // the sample index rides on gridDim.y: launches of at most 65535 samples
+    for (int32_t at = 0; at < B; at += 65535) {
+        const int nb = std::min<int32_t>(B - at, 65535);
+        FovParams pp = p;
+        pp.obs = reinterpret_cast<float *>(reinterpret_cast<char *>(d_obs) + (size_t)at * row_bytes);
+        q.env = d_env + at;
+        q.index = d_index + at;
+        q.loc_out = d_fov_loc ? d_fov_loc + 2 * (size_t)at * glimpses : nullptr;
+        q.taken = d_taken ? d_taken + at : nullptr;
+        const dim3 grid(c.frame_stack, nb), block(kThreads);
+#define LAUNCH(MODE)                                                                                             \
+    do {                                                                                                         \
+        if (headline)                                                                                            \
+            hipLaunchKernelGGL((agx::k_history_memory<GS, MODE, OT>), grid, block, lds, S(stream), GS{}, pp, q); \
+        else                                                                                                     \
+            hipLaunchKernelGGL((agx::k_history_memory<GeomR, MODE, OT>), grid, block, lds, S(stream), gr, pp, q); \
+    } while (0)
+        with_obs_type(ctx->obs_type, [&](auto tag) {
+            using OT = decltype(tag);
+            if (c.out_mode == AGX_OUT_MASK)
+                LAUNCH(AGX_OUT_MASK);
+            else
+                LAUNCH(AGX_OUT_RESIZE);
+            return 0;
+        });
+#undef LAUNCH
+    }
+    AGX_HIP(ctx, hipGetLastError());
+    return AGX_OK;
+}
+
+}  // extern "C"

@@ -9,6 +9,7 @@
 //   k_fovea_fixed       K2  clip/rint sensory action, crop, {raw | mask-out | bilinear upsample}
 //   k_fovea_generic     K3/K4 peripheral squeeze-expand + paste, flexible (ragged) fovea
 //   k_history_push / k_history_observe  K5  frame history: append the newest ring frame / re-create a retained observation
+//   k_history_memory    K6  glimpse memory: the elementwise max of a sample's last P re-created observations
 //
 // Persistent per-env state (owned by the context, see agx_api.hip):
 //   ring  u8 [N][fs][oh][ow]   numerators k of the reference's float32 k/255 frames
@@ -22,6 +23,7 @@
 #include "agx_fov_common.h"
 #include "agx_k2_fixed.h"
 #include "agx_k5_history.h"
+#include "agx_k6_glimpse.h"
 #include "agx_k34_resample.h"
 #include "agx_k3_per3.h"
 #include "agx_k4_flex3.h"
