@@ -294,10 +294,12 @@ int with_planes(int planes, F &&f) {
 }
 int obs_elem_bytes(int t) { return t == AGX_OBS_F32 ? 4 : 2; }
 
+// the compile-time geometry of the fixed fovea's kernels (K2, K5, K6: GeomS<84, 84, 30, 30>)
+bool headline_fixed(const agx_config &c) { return c.obs_h == 84 && c.obs_w == 84 && c.fov_h == 30 && c.fov_w == 30; }
+
 size_t fixed_lds(const agx_config &c) {
-    // window rows u8 [fh][ow] (16-B padded) | ytab[oh] | H[fh][ow]   (the carve of fovea_fixed_body)
-    const size_t raw = ((size_t)c.fov_h * c.obs_w + 15) & ~(size_t)15;
-    size_t b = raw;
+    // window rows u8 [fh][ow] (16-B padded) | ytab[oh] | H[fh][ow]   (agx_fixed_phases.h: fixed_carve)
+    size_t b = (size_t)agx::fixed_pad(c.fov_h, c.obs_w);
     if (c.out_mode == AGX_OUT_RESIZE) b += (size_t)c.obs_h * sizeof(Tap) + (size_t)c.fov_h * c.obs_w * sizeof(float);
     return b;
 }
@@ -1144,7 +1146,7 @@ int agx_fovea_fixed(agx_ctx *ctx, const void *d_action, int action_dtype, const 
     FovParams p = fov_params(ctx, d_action, action_dtype, nullptr, d_mask, d_obs, d_fov_loc, nullptr);
     fov_range(ctx, p);
     const size_t lds = fixed_lds(c);
-    const bool headline = c.obs_h == 84 && c.obs_w == 84 && c.fov_h == 30 && c.fov_w == 30;
+    const bool headline = headline_fixed(c);
     using GS = GeomS<84, 84, 30, 30>;
     const GeomR gr{c.obs_h, c.obs_w, c.fov_h, c.fov_w};
     const dim3 grid(c.frame_stack * ctx->planes, ctx->rng_n), block(kThreads);

@@ -39,7 +39,10 @@ struct GeomR {
 // IEEE correctly-rounded single division (hipcc default -fhip-fp32-correctly-rounded-divide-sqrt;
 // tests/test_gpu_parity.py checks all 256 values bit for bit).
 __device__ __forceinline__ float unit(uint32_t k) { return (float)k / 255.0f; }
-
+// the four bytes of a dword (k_full, k_history_observe's full-frame form)
+__device__ __forceinline__ float4 unit4(uint32_t v) {
+    return make_float4(unit(v & 0xFF), unit((v >> 8) & 0xFF), unit((v >> 16) & 0xFF), unit(v >> 24));
+}
 
 
 // float32(k) / 255 correctly rounded without the division sequence: q = k * y, r = k - 255 q (exact in an FMA),
@@ -56,7 +59,7 @@ __host__ __device__ __forceinline__ float unit_fast(float k) {
 // _Float16.  The arithmetic is the f32 path's whatever OT; each value is rounded to nearest-even once, at the store (bf16: a
 // plain cast, v_cvt_pk_bf16_f32; f16: v_cvt_f16_f32 in the default round-to-nearest mode with f16 denormals kept), so a
 // 16-bit observation is bit for bit the f32 observation cast to OT.  One store unit = 4 outputs: a float4 (16 B per lane)
-// at f32, 8 B per lane at 16 bits (obs4_t); the stores: store_obs in agx_k2_fixed.h, k_full in agx_k0_stack.h, lane-linear as before.
+// at f32, 8 B per lane at 16 bits (obs4_t); the stores: store_obs in agx_obs_store.h, k_full in agx_k0_stack.h, lane-linear as before.
 template <class OT>
 using obs4_t = typename std::conditional<sizeof(OT) == 4, float4, uint2>::type;
 template <class OT>
@@ -76,6 +79,33 @@ __device__ __forceinline__ uint32_t uniform_load_u8(const uint8_t *ptr) {
     asm volatile("s_load_dword %0, %1, 0x0\n\ts_waitcnt lgkmcnt(0)" : "=s"(w) : "s"(aligned) : "memory");
     return (w >> (8 * (uint32_t)(a & 3))) & 0xFFu;
 }
+// The wider forms, same contract: wave-uniform, naturally aligned, written by an earlier launch.
+__device__ __forceinline__ int32_t uniform_load_i32(const int32_t *ptr) {
+    int32_t w;
+    asm volatile("s_load_dword %0, %1, 0x0\n\ts_waitcnt lgkmcnt(0)" : "=s"(w) : "s"(ptr) : "memory");
+    return w;
+}
+__device__ __forceinline__ int2 uniform_load_i32x2(const int32_t *ptr) {
+    int2 w;
+    asm volatile("s_load_dwordx2 %0, %1, 0x0\n\ts_waitcnt lgkmcnt(0)" : "=s"(w) : "s"(ptr) : "memory");
+    return w;
+}
+__device__ __forceinline__ int64_t uniform_load_i64(const int64_t *ptr) {
+    int2 w;
+    asm volatile("s_load_dwordx2 %0, %1, 0x0\n\ts_waitcnt lgkmcnt(0)" : "=s"(w) : "s"(ptr) : "memory");
+    return (int64_t)(((uint64_t)(uint32_t)w.y << 32) | (uint32_t)w.x);
+}
+// the age byte and the fov_loc of one history row (agx_k5_history.h), one wait
+__device__ __forceinline__ void uniform_load_age_loc(const uint8_t *age, const int32_t *loc, int &a, int2 &rc) {
+    const uintptr_t at = reinterpret_cast<uintptr_t>(age);
+    const uint32_t *aligned = reinterpret_cast<const uint32_t *>(at & ~(uintptr_t)3);
+    uint32_t w;
+    asm volatile("s_load_dword %0, %2, 0x0\n\ts_load_dwordx2 %1, %3, 0x0\n\ts_waitcnt lgkmcnt(0)"
+                 : "=&s"(w), "=&s"(rc)
+                 : "s"(aligned), "s"(loc)
+                 : "memory");
+    a = (int)((w >> (8 * (uint32_t)(at & 3))) & 0xFFu);
+}
 // 24-bit multiply at full rate.  hipcc lowers __mul24 / __umul24 to the quarter-rate v_mul_lo_u32
 // whenever it cannot prove the operand ranges itself; every product on this path fits (operands < 2^24,
 // result < 2^32).
@@ -94,12 +124,6 @@ __device__ __forceinline__ uint32_t mad_u24(uint32_t a, uint32_t b, uint32_t c) 
     uint32_t r;
     asm("v_mad_u32_u24 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
     return r;
-}
-
-__device__ __forceinline__ int32_t uniform_load_i32(const int32_t *ptr) {
-    int32_t w;
-    asm volatile("s_load_dword %0, %1, 0x0\n\ts_waitcnt lgkmcnt(0)" : "=s"(w) : "s"(ptr) : "memory");
-    return w;
 }
 
 

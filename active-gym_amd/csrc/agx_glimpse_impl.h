@@ -7,8 +7,7 @@ namespace {
 
 // the LDS carve of k_history_memory
 size_t memory_lds(const agx_config &c, int glimpses, bool headline) {
-    const size_t raw = ((size_t)c.fov_h * c.obs_w + 15) & ~(size_t)15;
-    size_t b = agx::kMemTableBytes + (size_t)glimpses * raw;
+    size_t b = agx::kMemTableBytes + (size_t)glimpses * agx::fixed_pad(c.fov_h, c.obs_w);
     if (c.out_mode == AGX_OUT_RESIZE) {
         b += (size_t)c.obs_h * sizeof(Tap) + 2 * (size_t)c.fov_h * c.obs_w * sizeof(float);
         if (!headline) b += (size_t)c.obs_h * c.obs_w * sizeof(float);      // the running maximum of the run-time geometry form
@@ -33,7 +32,7 @@ int agx_history_observe_memory(agx_history *h, int32_t glimpses, const int32_t *
     if (c.out_mode == AGX_OUT_RAW)
         return fail(ctx, AGX_E_STATE, "agx_history_observe_memory: raw-crop mode is not served (a maximum over crops at different positions means nothing; mask-out and resize_to_full are)");
     if (!full_range(ctx)) return hist_refuse_range(h, "agx_history_observe_memory");
-    const bool headline = c.obs_h == 84 && c.obs_w == 84 && c.fov_h == 30 && c.fov_w == 30;
+    const bool headline = headline_fixed(c);
     const size_t lds = memory_lds(c, glimpses, headline);
     if (lds > kMaxLds)
         return fail(ctx, AGX_E_STATE, "agx_history_observe_memory: %d glimpses of this geometry need %zu B of LDS per workgroup (limit %zu)", glimpses, lds,

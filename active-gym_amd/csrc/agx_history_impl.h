@@ -147,7 +147,7 @@ int agx_history_observe(agx_history *h, int what, const int32_t *d_env, const in
     q.has_loc = fixed ? 1 : 0;
     const int mode = what == AGX_HIST_FULL ? agx::kHistFull : c.out_mode;
     const size_t lds = what == AGX_HIST_FULL ? 0 : fixed_lds(c);
-    const bool headline = c.obs_h == 84 && c.obs_w == 84 && c.fov_h == 30 && c.fov_w == 30;
+    const bool headline = headline_fixed(c);
     using GS = GeomS<84, 84, 30, 30>;
     const GeomR gr{c.obs_h, c.obs_w, c.fov_h, c.fov_w};
     const bool crop = what == AGX_HIST_FOVEA && c.out_mode == AGX_OUT_RAW;

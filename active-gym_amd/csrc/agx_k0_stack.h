@@ -40,7 +40,7 @@ __global__ __launch_bounds__(kThreads) void k_set_stack(StackParams p) {
     reinterpret_cast<uint32_t *>(p.ring)[o] = reinterpret_cast<const uint32_t *>(p.in_u8)[o];
 }
 
-// OT: the observation element type (agx_k2_fixed.h, obs4_t): at 16 bits each lane stores its 4 outputs as 8 B, lane-linear
+// OT: the observation element type (agx_common.h, obs4_t): at 16 bits each lane stores its 4 outputs as 8 B, lane-linear
 template <class OT = float, int NC = 1>
 __global__ __launch_bounds__(kThreads) void k_full(StackParams p) {
     const int n = blockIdx.z, y = blockIdx.y, j = y / NC, ch = y - j * NC;
@@ -49,12 +49,8 @@ __global__ __launch_bounds__(kThreads) void k_full(StackParams p) {
     int slot = p.head[n] + j;
     if (slot >= p.fs) slot -= p.fs;
     const uint32_t v = (reinterpret_cast<const uint32_t *>(p.ring) + (((size_t)n * p.fs + slot) * NC + ch) * p.words)[i];
-    float4 o;
-    o.x = unit(v & 0xFF);
-    o.y = unit((v >> 8) & 0xFF);
-    o.z = unit((v >> 16) & 0xFF);
-    o.w = unit(v >> 24);
-    // write-once observation stream: written through (sc1) like the fovea kernels' (store_obs, agx_k2_fixed.h); the frame of
+    const float4 o = unit4(v);
+    // write-once observation stream: written through (sc1) like the fovea kernels' (store_obs, agx_obs_store.h); the frame of
     // (n, y) is the buffer - wave-uniform by construction
     const uintptr_t a = reinterpret_cast<uintptr_t>(reinterpret_cast<obs4_t<OT> *>(p.out_f32) + ((size_t)n * p.fs * NC + y) * p.words);
     const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)a), hi = __builtin_amdgcn_readfirstlane((uint32_t)(a >> 32));

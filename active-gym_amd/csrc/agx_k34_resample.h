@@ -2,7 +2,7 @@
 // and the tuned host-table forms.
 #pragma once
 #include "agx_fov_common.h"
-#include "agx_k2_fixed.h"
+#include "agx_obs_store.h"
 
 namespace agx {
 

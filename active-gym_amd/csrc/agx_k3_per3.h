@@ -11,7 +11,7 @@
 // the periphery carries the 1/255 in the W-squeeze weights.  LDS 18 KB for the headline -> 8 workgroups per CU.
 #pragma once
 #include "agx_fov_common.h"
-#include "agx_k2_fixed.h"
+#include "agx_obs_store.h"
 
 namespace agx {
 

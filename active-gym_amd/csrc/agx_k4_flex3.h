@@ -22,7 +22,7 @@
 // plain path | row taps: 21.5 KB for 84x84 / 30x30 -> 7 workgroups per CU.
 #pragma once
 #include "agx_fov_common.h"
-#include "agx_k2_fixed.h"
+#include "agx_obs_store.h"
 
 namespace agx {
 

@@ -20,7 +20,7 @@
 // any N <= 65,535.
 #pragma once
 #include "agx_fov_common.h"
-#include "agx_k2_fixed.h"
+#include "agx_obs_store.h"
 #include "agx_k4_flex3.h"
 
 namespace agx {

@@ -1,7 +1,9 @@
 // agx_k5_history.h - K5: the frame history (include/agx_history.h): k_history_push appends each env's newest ring frame,
-// k_history_observe re-creates the observation of retained env-steps with K2's own phases (agx_k2_fixed.h).
+// k_history_observe re-creates the observation of retained env-steps by running the fixed fovea's phases (agx_fixed_phases.h,
+// the ones K2 runs) on history rows.
 #pragma once
-#include "agx_k2_fixed.h"
+#include "agx_fixed_phases.h"
+#include "agx_fov_common.h"
 
 namespace agx {
 
@@ -16,17 +18,6 @@ struct HistParams {
                          // clear: unknown frames before it, so its first fs - 1 samples stay invalid until a CLEAR)
 };
 
-// wave-uniform 8-byte loads through the scalar cache (uniform_load_i32's contract: written by an earlier launch, naturally aligned)
-__device__ __forceinline__ int64_t uniform_load_i64(const int64_t *ptr) {
-    int2 w;
-    asm volatile("s_load_dwordx2 %0, %1, 0x0\n\ts_waitcnt lgkmcnt(0)" : "=s"(w) : "s"(ptr) : "memory");
-    return (int64_t)(((uint64_t)(uint32_t)w.y << 32) | (uint32_t)w.x);
-}
-__device__ __forceinline__ int2 uniform_load_i32x2(const int32_t *ptr) {
-    int2 w;
-    asm volatile("s_load_dwordx2 %0, %1, 0x0\n\ts_waitcnt lgkmcnt(0)" : "=s"(w) : "s"(ptr) : "memory");
-    return w;
-}
 // index mod T (indices below 2^31 - every history younger than two billion appends per env - take the 32-bit form)
 __device__ __forceinline__ int hist_row(int64_t k, int T) {
     return (k >> 31) == 0 ? (int)((uint32_t)k % (uint32_t)T) : (int)(k % T);
@@ -83,13 +74,29 @@ __global__ __launch_bounds__(kThreads) void k_history_last(const int64_t *count,
     if (n < n_envs) out[n] = count[n] - 1;
 }
 
+// A sample b = (env n, index k) of the history, as k_history_observe and k_history_memory resolve it (scalar loads: everything is
+// workgroup-uniform).  ok: n is an env and row k is still retained; cnt = the env's appends so far (0 if n is no env).
+struct HistSample {
+    int n;
+    int64_t k, cnt;
+    bool ok;
+};
+__device__ __forceinline__ HistSample hist_sample(const int32_t *env, const int64_t *index, const HistParams &h, int b) {
+    HistSample s{uniform_load_i32(env + b), uniform_load_i64(index + b), 0, false};
+    if (s.n >= 0 && s.n < h.N && s.k >= 0) {
+        s.cnt = uniform_load_i64(h.count + s.n);
+        s.ok = s.k < s.cnt && s.k >= s.cnt - h.T;
+    }
+    return s;
+}
+
 // ---------------------------------------------------------------------------------------------
 // k_history_observe<G, MODE, OT>: grid = (fs, B), block = 256.  Workgroup (j, b) owns stack position j of sample b directly
-// (no ring head here): it resolves the sample (env, index, count, age: scalar loads), leaves an invalid one untouched, and
-// otherwise fetches only the fh window rows of history row k - (fs-1-j) - nothing for a frame older than the env's last CLEAR,
-// whose LDS image is zeros - and runs K2's phases on them as fovea_fixed_body does: the context's own xtab / ytab, unit_fast,
-// the explicit mul + fma lerps, store_obs / store_packed (sc1 buffer stores).  Same arithmetic on the same bytes: the output
-// of a sample at its recorded fov_loc is bit for bit the step's.  MODE = kHistFull: the full-frame k/255 write of k_full.
+// (no ring head here): it resolves the sample and the age of row k, leaves an invalid one untouched, and otherwise fetches
+// only the fh window rows of history row k - (fs-1-j) - nothing for a frame older than the env's last CLEAR, whose LDS image
+// is zeros - and runs the shared phases on them with the context's own xtab / ytab.  The phases are the very code
+// fovea_fixed_body runs, so the output of a sample at its recorded fov_loc is bit for bit the step's.  MODE = kHistFull: the
+// full-frame k/255 write of k_full.
 // FovParams carries what K2's carries (obs, user_loc, xtab, ytab, action, action_dt; relative = 0: a read-time action is
 // absolute); the action row is b's.
 // ---------------------------------------------------------------------------------------------
@@ -110,15 +117,11 @@ __global__ __launch_bounds__(kThreads) void k_history_observe(G g, FovParams p, 
     const int j = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
     const int oh = g.oh(), ow = g.ow(), fh = g.fh(), fw = g.fw();
     const int T = q.h.T, N = q.h.N, fs = q.h.fs;
-    // ---- the sample: env, index, the env's count, the age of row k.  Everything is workgroup-uniform.
-    const int n = uniform_load_i32(q.env + b);
-    const int64_t k = uniform_load_i64(q.index + b);
-    bool ok = n >= 0 && n < N && k >= 0;
-    int64_t cnt = 0;
-    if (ok) {
-        cnt = uniform_load_i64(q.h.count + n);
-        ok = k < cnt && k >= cnt - T;
-    }
+    // ---- the sample, and the age of row k
+    const HistSample s = hist_sample(q.env, q.index, q.h, b);
+    const int n = s.n;
+    const int64_t k = s.k, cnt = s.cnt;
+    bool ok = s.ok;
     int row_k = 0, age = 0;
     if (ok) {
         row_k = hist_row(k, T);
@@ -178,104 +181,36 @@ __global__ __launch_bounds__(kThreads) void k_history_observe(G g, FovParams p, 
         // the base observation: k_full's arithmetic (unit: the IEEE quotient) and its written-through store
         obs4_t<OT> *out4 = reinterpret_cast<obs4_t<OT> *>(p.obs) + ((size_t)b * fs + j) * (size_t)(oh * ow4);
         const auto oout = obs_out<OT>(out4, oh * ow4);
-        for (int i = tid; i < oh * ow4; i += kThreads) {
-            const uint32_t v = zero ? 0u : fsrc[i];
-            float4 o;
-            o.x = unit(v & 0xFF);
-            o.y = unit((v >> 8) & 0xFF);
-            o.z = unit((v >> 16) & 0xFF);
-            o.w = unit(v >> 24);
-            store_obs(oout, i, o);
-        }
+        for (int i = tid; i < oh * ow4; i += kThreads) store_obs(oout, i, unit4(zero ? 0u : fsrc[i]));
         return;
     }
-    // LDS carve: window rows u8 [fh][ow] (16-B padded) | ytab[oh] | H[fh][ow]     (fovea_fixed_body's; agx_api.hip: fixed_lds)
-    unsigned char *raw = smem;
-    const int raw_pad = (fh * ow + 15) & ~15;
-    Tap *ytab_s = reinterpret_cast<Tap *>(raw + raw_pad);
-    float *H = reinterpret_cast<float *>(ytab_s + oh);
-    const int wp = ow;
+    const FixedCarve lds = fixed_carve(smem, oh, ow, fh);            // (agx_api.hip: fixed_lds)
     {
         const uint32_t *wsrc = fsrc + r * ow4;
         const int wwords = (fh * ow) >> 2;
-        constexpr int kW = 3;
-        uint32_t ww[kW];
+        uint32_t ww[kWinRegs];
 #pragma unroll
-        for (int k_ = 0; k_ < kW; ++k_) ww[k_] = zero ? 0u : wsrc[min(tid + k_ * kThreads, wwords - 1)];
-        if (MODE == AGX_OUT_RESIZE) {
-            if (tid < oh) *reinterpret_cast<int4 *>(ytab_s + tid) = yt0;
-            for (int i = tid + kThreads; i < oh; i += kThreads) ytab_s[i] = p.ytab[i];
-        }
-#pragma unroll
-        for (int k_ = 0; k_ < kW; ++k_)
-            if (tid + k_ * kThreads < wwords) reinterpret_cast<uint32_t *>(raw)[tid + k_ * kThreads] = ww[k_];
-        for (int i = tid + kW * kThreads; i < wwords; i += kThreads) reinterpret_cast<uint32_t *>(raw)[i] = zero ? 0u : wsrc[i];
+        for (int k = 0; k < kWinRegs; ++k) ww[k] = window_reg(wsrc, k, wwords, tid, zero);
+        if (MODE == AGX_OUT_RESIZE) ytab_stage(lds.ytab_s, yt0, p.ytab, oh, tid);
+        window_land(lds.raw, ww, wwords, tid);
+        window_tail(lds.raw, wsrc, wwords, tid, zero);
         __syncthreads();
     }
-    const int xcol = tid % ow, yb = tid / ow;
-    const unsigned char *win = raw + c;
+    const unsigned char *win = lds.raw + c;
     if (MODE == AGX_OUT_RAW) {
-        const auto cout = packed_out<OT>(reinterpret_cast<OT *>(p.obs) + ((size_t)b * fs + j) * (size_t)(fh * fw), fh * fw);
-        for (int i = tid; i < fh * fw; i += kThreads) {
-            const int y = i / fw, x = i - y * fw;
-            store_packed(cout, i, unit_fast((float)win[y * wp + x]));
-        }
+        raw_crop_write(reinterpret_cast<OT *>(p.obs) + ((size_t)b * fs + j) * (size_t)(fh * fw), win, ow, fh, fw, tid);
         return;
     }
     obs4_t<OT> *out4 = reinterpret_cast<obs4_t<OT> *>(p.obs) + ((size_t)b * fs + j) * (size_t)(oh * ow4);
     const auto oout = obs_out<OT>(out4, oh * ow4);
     if (MODE == AGX_OUT_MASK) {
-        for (int k_ = 0; k_ < (oh * ow4 + kThreads - 1) / kThreads; ++k_) {
-            const int qd = tid + k_ * kThreads;
-            if (qd >= oh * ow4) break;
-            const int yrow = qd / ow4, x = (qd - yrow * ow4) * 4;
-            float v[4] = {0.f, 0.f, 0.f, 0.f};
-            if (yrow >= r && yrow < r + fh && x + 3 >= c && x < c + fw) {
-                const uint32_t w = *reinterpret_cast<const uint32_t *>(raw + (yrow - r) * wp + x);
-#pragma unroll
-                for (int e = 0; e < 4; ++e)
-                    if (x + e >= c && x + e < c + fw) v[e] = unit_fast((float)((w >> (8 * e)) & 0xFF));
-            }
-            store_obs(oout, qd, make_float4(v[0], v[1], v[2], v[3]));
-        }
+        mask_out_write(oout, lds.raw, r, c, oh, ow, fh, fw, tid);
         return;
     }
-    // ---- RESIZE, phase C: thread owns column xcol (taps in registers), rows yb, yb + rstep, ...
-    const int rstep = kThreads / ow;
-    if (rstep > 0) {
-        if (yb < rstep) {
-            const unsigned char *c0 = win + xt.x, *c1 = win + xt.y;
-            const float wa = __int_as_float(xt.z), wb = __int_as_float(xt.w);
-#pragma unroll 10
-            for (int y = yb; y < fh; y += rstep)
-                H[y * ow + xcol] = fmaf(wb, unit_fast((float)c1[y * wp]), wa * unit_fast((float)c0[y * wp]));
-        }
-    } else {                                                          // ow > 256: generic striding
-        for (int i = tid; i < fh * ow; i += kThreads) {
-            const int y = i / ow, x = i - y * ow;
-            const Tap t = p.xtab[x];
-            H[i] = fmaf(t.b, unit_fast((float)win[y * wp + t.aux]), t.a * unit_fast((float)win[y * wp + t.lo]));
-        }
-    }
+    const int xcol = tid % ow, yb = tid / ow;
+    phase_c(lds.H, win, xt, p.xtab, ow, fh, xcol, yb, tid);
     __syncthreads();
-    // ---- phase D: each output float4 is the vertical lerp (mul + fma, as K2 writes it) of two ds_read_b128
-    const float4 *H4 = reinterpret_cast<const float4 *>(H);
-    const int nq = oh * ow4, passes = (nq + kThreads - 1) / kThreads;
-#pragma unroll 7
-    for (int k_ = 0; k_ < passes; ++k_) {
-        const int qd = tid + k_ * kThreads;
-        if (qd >= nq) break;
-        const int yrow = qd / ow4, x4 = qd - yrow * ow4;
-        const Tap t = ytab_s[yrow];
-        const float4 a = H4[t.lo * ow4 + x4];
-        const float4 bb = H4[t.aux * ow4 + x4];
-        float4 o;
-        o.x = fmaf(t.b, bb.x, t.a * a.x);
-        o.y = fmaf(t.b, bb.y, t.a * a.y);
-        o.z = fmaf(t.b, bb.z, t.a * a.z);
-        o.w = fmaf(t.b, bb.w, t.a * a.w);
-        store_obs(oout, qd, o);
-    }
+    phase_d_write(oout, lds.H, lds.ytab_s, oh, ow4, tid);
 }
 
 }  // namespace agx

@@ -1,5 +1,6 @@
 // agx_k6_glimpse.h - K6: the glimpse memory (include/agx_glimpse.h): k_history_memory writes the elementwise maximum of a
-// sample's last P observations, each re-created from the frame history as k_history_observe (agx_k5_history.h) does.
+// sample's last P observations, each re-created from the frame history by the fixed fovea's phases (agx_fixed_phases.h), as
+// k_history_observe (agx_k5_history.h) re-creates one.
 #pragma once
 #include "agx_glimpse.h"
 #include "agx_k5_history.h"
@@ -14,18 +15,6 @@ struct HistMemParams {
     uint8_t *taken;           // [B] or nullptr
     int32_t glimpses;         // P, 1 .. AGX_GLIMPSE_LIMIT
 };
-
-// the age byte and the fov_loc of one history row, one wait
-__device__ __forceinline__ void uniform_load_age_loc(const uint8_t *age, const int32_t *loc, int &a, int2 &rc) {
-    const uintptr_t at = reinterpret_cast<uintptr_t>(age);
-    const uint32_t *aligned = reinterpret_cast<const uint32_t *>(at & ~(uintptr_t)3);
-    uint32_t w;
-    asm volatile("s_load_dword %0, %2, 0x0\n\ts_load_dwordx2 %1, %3, 0x0\n\ts_waitcnt lgkmcnt(0)"
-                 : "=&s"(w), "=&s"(rc)
-                 : "s"(aligned), "s"(loc)
-                 : "memory");
-    a = (int)((w >> (8 * (uint32_t)(at & 3))) & 0xFFu);
-}
 
 // Where the running maximum of the resize form lives: in registers when the number of output passes is a compile-time
 // constant (the headline geometry: 7 float4 per thread), in an LDS image [oh][ow] f32 otherwise.
@@ -47,10 +36,10 @@ struct MemPasses<GeomS<OH, OW, FH, FW>> {
 //            k - i - (fs-1-j) into an LDS image of its own (zeros for a frame older than that glimpse's last CLEAR); the
 //            loads of all glimpses are in flight together, one barrier.
 //   MASK:    an output byte is the max over the glimpses whose window covers it; unit_fast is monotone: one conversion.
-//   RESIZE:  per glimpse K2's phase C (H, double-buffered: one barrier per glimpse) and phase D with the running maximum;
+//   RESIZE:  per glimpse phase C (H, double-buffered: one barrier per glimpse) and phase D with the running maximum;
 //            one pass of store_obs at the end.  The first glimpse assigns, so P = 1 is k_history_observe bit for bit.
 // LDS carve: glimpse table int2[AGX_GLIMPSE_LIMIT] (r, c) | P windows u8 [fh][ow] (16-B padded each) | ytab[oh] | H[2][fh][ow]
-//            | acc[oh][ow] (run-time geometry only)            (agx_glimpse_impl.h: memory_lds)
+//            (fixed_carve with P windows) | acc[oh][ow] (run-time geometry only)            (agx_glimpse_impl.h: memory_lds)
 // ---------------------------------------------------------------------------------------------
 constexpr int kMemTableBytes = AGX_GLIMPSE_LIMIT * 16;
 
@@ -62,27 +51,20 @@ __global__ __launch_bounds__(kThreads) void k_history_memory(G g, FovParams p, H
     const int oh = g.oh(), ow = g.ow(), fh = g.fh(), fw = g.fw();
     const int T = q.h.T, N = q.h.N, fs = q.h.fs, P = q.glimpses;
     // ---- the sample, as k_history_observe resolves it
-    const int n = uniform_load_i32(q.env + b);
-    const int64_t k = uniform_load_i64(q.index + b);
-    bool ok = n >= 0 && n < N && k >= 0;
-    int64_t cnt = 0;
-    if (ok) {
-        cnt = uniform_load_i64(q.h.count + n);
-        ok = k < cnt && k >= cnt - T;
-    }
-    if (!ok) {
+    const HistSample s = hist_sample(q.env, q.index, q.h, b);
+    if (!s.ok) {
         if (j == 0 && tid == 0 && q.taken) q.taken[b] = 0;
         return;
     }
-    const int64_t oldest = cnt - T > 0 ? cnt - T : 0;     // the oldest retained index
+    const int n = s.n;
+    const int64_t k = s.k, oldest = s.cnt - T > 0 ? s.cnt - T : 0;     // the oldest retained index
     const int row_k = hist_row(k, T);
     const int back = fs - 1 - j;
     const int fbytes = oh * ow, ow4 = ow >> 2;
-    const int raw_pad = (fh * ow + 15) & ~15;
+    const int raw_pad = fixed_pad(fh, ow);
     const int wwords = (fh * ow) >> 2;
     int2 *tab = reinterpret_cast<int2 *>(smem);
-    unsigned char *raw0 = smem + kMemTableBytes;
-    Tap *ytab_s = reinterpret_cast<Tap *>(raw0 + P * raw_pad);
+    const FixedCarve lds = fixed_carve(smem + kMemTableBytes, oh, ow, fh, P);
 
     int4 xt = make_int4(0, 0, 0, 0);
     int4 yt0 = make_int4(0, 0, 0, 0);
@@ -91,14 +73,13 @@ __global__ __launch_bounds__(kThreads) void k_history_memory(G g, FovParams p, H
         yt0 = *reinterpret_cast<const int4 *>(p.ytab + min(tid, oh - 1));
     }
     // ---- staging: resolve glimpse i, issue its window loads; the LDS writes follow once every glimpse's loads are out
-    constexpr int kW = 3;
-    uint32_t ww[AGX_GLIMPSE_LIMIT][kW];
+    uint32_t ww[AGX_GLIMPSE_LIMIT][kWinRegs];
     int nt = 0, age_k = 0;
     bool live = true;
 #pragma unroll
     for (int i = 0; i < AGX_GLIMPSE_LIMIT; ++i) {
 #pragma unroll
-        for (int k_ = 0; k_ < kW; ++k_) ww[i][k_] = 0u;
+        for (int k_ = 0; k_ < kWinRegs; ++k_) ww[i][k_] = 0u;
         if (live && i < P && k - i >= oldest) {
             int row_i = row_k - i;                        // i < AGX_GLIMPSE_LIMIT; T may be smaller
             while (row_i < 0) row_i += T;
@@ -116,15 +97,15 @@ __global__ __launch_bounds__(kThreads) void k_history_memory(G g, FovParams p, H
                     tab[i] = make_int2(r, c);
                     if (j == 0 && q.loc_out) *reinterpret_cast<int2 *>(q.loc_out + 2 * ((size_t)b * P + i)) = make_int2(r, c);
                 }
-                if (back <= age_i) {                      // else: a frame older than this glimpse's last CLEAR, zeros
+                if (back <= age_i) {
                     int row = row_i - back;               // back <= fs - 1 < T
                     if (row < 0) row += T;
                     const uint32_t *wsrc = reinterpret_cast<const uint32_t *>(q.h.frames + ((size_t)row * N + n) * (size_t)fbytes) + r * ow4;
 #pragma unroll
-                    for (int k_ = 0; k_ < kW; ++k_) ww[i][k_] = wsrc[min(tid + k_ * kThreads, wwords - 1)];
-                    for (int w = tid + kW * kThreads; w < wwords; w += kThreads) reinterpret_cast<uint32_t *>(raw0 + i * raw_pad)[w] = wsrc[w];
-                } else {
-                    for (int w = tid + kW * kThreads; w < wwords; w += kThreads) reinterpret_cast<uint32_t *>(raw0 + i * raw_pad)[w] = 0u;
+                    for (int k_ = 0; k_ < kWinRegs; ++k_) ww[i][k_] = window_reg(wsrc, k_, wwords, tid);
+                    window_tail(lds.raw + i * raw_pad, wsrc, wwords, tid);
+                } else {                                  // a frame older than this glimpse's last CLEAR: zeros
+                    window_tail(lds.raw + i * raw_pad, nullptr, wwords, tid, /*zero*/ true);
                 }
             }
         } else {
@@ -133,20 +114,12 @@ __global__ __launch_bounds__(kThreads) void k_history_memory(G g, FovParams p, H
     }
     if (j == 0 && tid == 0 && q.taken) q.taken[b] = (uint8_t)nt;
     if (nt == 0) return;
-    if (MODE == AGX_OUT_RESIZE) {
-        if (tid < oh) *reinterpret_cast<int4 *>(ytab_s + tid) = yt0;
-        for (int i = tid + kThreads; i < oh; i += kThreads) ytab_s[i] = p.ytab[i];
-    }
+    if (MODE == AGX_OUT_RESIZE) ytab_stage(lds.ytab_s, yt0, p.ytab, oh, tid);
 #pragma unroll
     for (int i = 0; i < AGX_GLIMPSE_LIMIT; ++i)
-        if (i < nt) {
-#pragma unroll
-            for (int k_ = 0; k_ < kW; ++k_)
-                if (tid + k_ * kThreads < wwords) reinterpret_cast<uint32_t *>(raw0 + i * raw_pad)[tid + k_ * kThreads] = ww[i][k_];
-        }
+        if (i < nt) window_land(lds.raw + i * raw_pad, ww[i], wwords, tid);
     __syncthreads();
 
-    const int wp = ow;
     const int nq = oh * ow4, passes = (nq + kThreads - 1) / kThreads;
     obs4_t<OT> *out4 = reinterpret_cast<obs4_t<OT> *>(p.obs) + ((size_t)b * fs + j) * (size_t)nq;
     const auto oout = obs_out<OT>(out4, nq);
@@ -160,7 +133,7 @@ __global__ __launch_bounds__(kThreads) void k_history_memory(G g, FovParams p, H
                 const int2 rc = tab[i];
                 const int r = rc.x, c = rc.y;
                 if (yrow >= r && yrow < r + fh && x + 3 >= c && x < c + fw) {
-                    const uint32_t w = *reinterpret_cast<const uint32_t *>(raw0 + i * raw_pad + (yrow - r) * wp + x);
+                    const uint32_t w = *reinterpret_cast<const uint32_t *>(lds.raw + i * raw_pad + (yrow - r) * ow + x);
 #pragma unroll
                     for (int e = 0; e < 4; ++e)
                         if (x + e >= c && x + e < c + fw) m[e] = max(m[e], (w >> (8 * e)) & 0xFFu);
@@ -173,49 +146,23 @@ __global__ __launch_bounds__(kThreads) void k_history_memory(G g, FovParams p, H
     // ---- RESIZE
     constexpr int kRegPasses = MemPasses<G>::value;
     constexpr bool kRegs = kRegPasses > 0 && kRegPasses <= 8;
-    float *H0 = reinterpret_cast<float *>(ytab_s + oh);
-    float4 *accL = reinterpret_cast<float4 *>(H0 + 2 * fh * ow);      // run-time geometry: this thread's own quads only
+    float4 *accL = reinterpret_cast<float4 *>(lds.H + 2 * fh * ow);   // run-time geometry: this thread's own quads only
     float4 acc[kRegs ? kRegPasses : 1];
     const int xcol = tid % ow, yb = tid / ow;
-    const int rstep = kThreads / ow;
     for (int i = 0; i < nt; ++i) {
         const int c = __builtin_amdgcn_readfirstlane(tab[i].y);
-        const unsigned char *win = raw0 + i * raw_pad + c;
-        float *H = H0 + (i & 1) * (fh * ow);
-        // phase C: thread owns column xcol (taps in registers), rows yb, yb + rstep, ...
-        if (rstep > 0) {
-            if (yb < rstep) {
-                const unsigned char *c0 = win + xt.x, *c1 = win + xt.y;
-                const float wa = __int_as_float(xt.z), wb = __int_as_float(xt.w);
-#pragma unroll 10
-                for (int y = yb; y < fh; y += rstep)
-                    H[y * ow + xcol] = fmaf(wb, unit_fast((float)c1[y * wp]), wa * unit_fast((float)c0[y * wp]));
-            }
-        } else {                                                      // ow > 256: generic striding
-            for (int e = tid; e < fh * ow; e += kThreads) {
-                const int y = e / ow, x = e - y * ow;
-                const Tap t = p.xtab[x];
-                H[e] = fmaf(t.b, unit_fast((float)win[y * wp + t.aux]), t.a * unit_fast((float)win[y * wp + t.lo]));
-            }
-        }
+        float *H = lds.H + (i & 1) * (fh * ow);
+        phase_c(H, lds.raw + i * raw_pad + c, xt, p.xtab, ow, fh, xcol, yb, tid);
         // one barrier per glimpse: phase C of glimpse i + 1 writes the other H, and whoever writes this H again (glimpse
         // i + 2) has passed the barrier of glimpse i + 1, behind every thread's phase D of glimpse i
         __syncthreads();
-        // phase D: the vertical lerp (mul + fma, as K2 writes it) of two ds_read_b128, maxed into the running maximum
+        // phase D, maxed into the running maximum
         const float4 *H4 = reinterpret_cast<const float4 *>(H);
         if constexpr (kRegs) {
 #pragma unroll
             for (int k_ = 0; k_ < kRegPasses; ++k_) {
                 const int qd = min(tid + k_ * kThreads, nq - 1);
-                const int yrow = qd / ow4, x4 = qd - yrow * ow4;
-                const Tap t = ytab_s[yrow];
-                const float4 a = H4[t.lo * ow4 + x4];
-                const float4 bb = H4[t.aux * ow4 + x4];
-                float4 o;
-                o.x = fmaf(t.b, bb.x, t.a * a.x);
-                o.y = fmaf(t.b, bb.y, t.a * a.y);
-                o.z = fmaf(t.b, bb.z, t.a * a.z);
-                o.w = fmaf(t.b, bb.w, t.a * a.w);
+                const float4 o = phase_d_quad(H4, lds.ytab_s, qd, ow4);
                 if (i == 0) {
                     acc[k_] = o;
                 } else {
@@ -229,15 +176,7 @@ __global__ __launch_bounds__(kThreads) void k_history_memory(G g, FovParams p, H
             for (int k_ = 0; k_ < passes; ++k_) {
                 const int qd = tid + k_ * kThreads;
                 if (qd >= nq) break;
-                const int yrow = qd / ow4, x4 = qd - yrow * ow4;
-                const Tap t = ytab_s[yrow];
-                const float4 a = H4[t.lo * ow4 + x4];
-                const float4 bb = H4[t.aux * ow4 + x4];
-                float4 o;
-                o.x = fmaf(t.b, bb.x, t.a * a.x);
-                o.y = fmaf(t.b, bb.y, t.a * a.y);
-                o.z = fmaf(t.b, bb.z, t.a * a.z);
-                o.w = fmaf(t.b, bb.w, t.a * a.w);
+                float4 o = phase_d_quad(H4, lds.ytab_s, qd, ow4);
                 if (i > 0) {
                     const float4 m = accL[qd];
                     o.x = fmaxf(m.x, o.x);

@@ -286,9 +286,11 @@ def test_low_occupancy(mode, N):
 
 # ---- case 5: the run-time geometry form
 @pytest.mark.parametrize("mode", ["mask", "resize"])
-@pytest.mark.parametrize("obs, fov, fs", [((100, 100), (30, 20), 3), ((128, 128), (31, 9), 1)], ids=["100x100-30x20-fs3", "128x128-31x9-fs1"])
+@pytest.mark.parametrize("obs, fov, fs", [((100, 100), (30, 20), 3), ((128, 128), (31, 9), 1), ((8, 264), (4, 100), 3)],
+                         ids=["100x100-30x20-fs3", "128x128-31x9-fs1", "8x264-4x100-fs3"])
 def test_generic_geometry(obs, fov, fs, mode):
-    """k_fovea_fixed<GeomR> geometries of tests/golden/geometry_cases.json with a non-square window: the LDS accumulator."""
+    """k_fovea_fixed<GeomR> geometries of tests/golden/geometry_cases.json with a non-square window: the LDS accumulator.
+    8 x 264: the ow > 256 striding horizontal pass together with it."""
     from active_gym import FrameHistory
     assert any(tuple(c["obs"]) == obs and tuple(c["fov"]) == fov and c["fs"] == fs and "GeomR" in c["plan"].get("fixed_" + mode, "") for c in CASES)
     pipe = _pipe(4, obs=obs, fov=fov, fs=fs, mode=mode)

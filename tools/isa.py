@@ -1,12 +1,16 @@
 #!/usr/bin/env python3
-"""tools/isa.py <kernel-substring> [--dump] - compile agx_api.hip with -save-temps (in /tmp/agx_isa) and print the
+"""tools/isa.py <kernel-substring> [--dump] [--src DIR] - compile agx_api.hip with -save-temps (in /tmp/agx_isa) and print the
 instruction histogram, register use and (with --dump) the ISA of every kernel whose mangled name contains the substring.
     python tools/isa.py k_ingest_full12
+--src DIR: the tree to compile (a checkout of another commit, to compare against), into /tmp/agx_isa_<name of DIR>.
 """
 import collections, os, re, subprocess, sys
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 OUT = "/tmp/agx_isa"
 def main():
+    global REPO, OUT
+    if "--src" in sys.argv:
+        REPO = os.path.abspath(sys.argv[sys.argv.index("--src") + 1]); OUT += "_" + os.path.basename(REPO)
     pat = sys.argv[1]; dump = "--dump" in sys.argv; table = "--table" in sys.argv      # --table: one line per kernel (pat "" = all)
     extra = [a for a in sys.argv[2:] if a.startswith("-D")]
     os.makedirs(OUT, exist_ok=True)
