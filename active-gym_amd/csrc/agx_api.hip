@@ -18,6 +18,7 @@
 #include "agx.h"
 #include "agx_kernels.h"
 #include "agx_host_tables.h"
+#include "agx_plan.h"
 #include "agx_device_guard.h"
 #include "agx_range.h"
 
@@ -52,20 +53,18 @@ struct agx_ctx {
     int2 *flex_ln[6] = {};
     float *flex_w[6] = {};
     int4 *flex_meta[6] = {};
-    size_t flex_tab_floats = 0;   // worst-case LDS floats of the staged tables
     // K4 resize_to_full form (k_fovea_flexible3): composed per-axis operators, see agx_k4_flex3.h
     Flex3Params f3{};
-    bool f3_ok = false;
     // K4 raw-crop / mask-out / packed forms (k_fovea_flexible_raw3, agx_k4_raw3.h)
     FlexRawParams fr{};
-    bool fr_ok = false;
-    size_t fr_lds = 0;
     int64_t *pack_local = nullptr;   // agx_fovea_flexible_packed: [N] block-local exclusive offsets, [ceil(N/256)] block totals
     int64_t *pack_block = nullptr;   // (both allocated in agx_create for flexible raw-crop contexts: no allocation in a step call)
     // K3 tuned form 3 (k_fovea_peripheral3)
     Per3Params p3{};
-    int p3_mt = 0;
-    size_t p3_lds = 0;
+    // What runs (agx_plan.h), computed once in agx_create: the fovea launch of the context's kind, and the K1 launch of each
+    // screen layout (K1Layout) at the band height in force for it
+    FovPlan plan;
+    K1Launch k1l[4];
     std::vector<void *> owned;    // further device allocations freed by agx_destroy
 #ifdef AGX_EXPERIMENTS
     // split step (agx_step_fixed): env-range parts 1.. run on these internal streams, forked from / joined to the caller's
@@ -80,12 +79,7 @@ struct agx_ctx {
     // several forms and compare them).  The shipped library has only the five that select a FALLBACK kernel, i.e. the
     // kernel (or launch sequence) other geometries get anyway (tests/test_gpu_parity.py::test_generic_fallback_kernel_matches_tuned); the rest
     // exist in the experiments build (-DAGX_EXPERIMENTS, experiments/agx_experiments.h) only.
-    struct Tune {
-        int generic = 0;         // AGX_FOVEA_GENERIC     K3 / K4 through the generic fallback kernel
-        int no_full = 0;         // AGX_INGEST_NO_FULL    general k_ingest<256> even where k_ingest_full12 applies
-        int flex_v2 = 0;         // AGX_FLEX_V2           K4 through k_fovea_flexible2 (pass-by-pass form)
-        int per_v2 = 0;          // AGX_PER_V2            K3 through k_fovea_peripheral2
-        int packed_unfused = 0;  // AGX_STEP_PACKED_UNFUSED  agx_step_flexible_packed as the three stand-alone launches
+    struct Tune : Knobs {        // the five shipped knobs: agx_plan.h
         // ---- experiments build only (always 0 in libagx.so)
         int ingest_t = 0;        // AGX_INGEST_T          128 | 256 threads per ingest workgroup
         int band_rows = 0;       // AGX_INGEST_BAND_ROWS  output rows per ingest workgroup (<= the default)
@@ -153,109 +147,6 @@ using DeviceGuard = agx::DeviceGuardT<HipDeviceApi>;      // agx_device_guard.h 
 
 inline hipStream_t S(void *s) { return static_cast<hipStream_t>(s); }
 
-// One axis of torchvision Resize (ATen upsample_bilinear2d, align_corners=False) as explicit taps:
-// antialiased triangle filter when down-scaling with antialias on (_compute_indices_min_size_weights_aa),
-// plain bilinear otherwise (area_pixel_compute_source_index); all in double, weights normalised.
-// compile-time tap bounds the tuned kernels are instantiated for (0 = run-time loops)
-int tap_bucket(int n) { return n <= 2 ? 2 : n <= 4 ? 4 : n <= 8 ? 8 : n <= 12 ? 12 : n <= 16 ? 16 : n; }
-
-void axis_taps(int n_in, int n_out, bool antialias, std::vector<int2> &ln, std::vector<float> &w, int &maxt) {
-    std::vector<std::vector<double>> ws(n_out);
-    ln.resize(n_out);
-    const double scale = (double)n_in / (double)n_out;
-    const bool aa = antialias && n_in > n_out;
-    maxt = 1;
-    for (int i = 0; i < n_out; ++i) {
-        if (aa) {
-            const double support = scale, invscale = 1.0 / scale, center = scale * (i + 0.5);
-            long long xmin = (long long)(center - support + 0.5);
-            if (xmin < 0) xmin = 0;
-            long long xmax = (long long)(center + support + 0.5);
-            if (xmax > n_in) xmax = n_in;
-            double total = 0.0;
-            for (long long jx = xmin; jx < xmax; ++jx) {
-                double x = ((double)jx - center + 0.5) * invscale;
-                if (x < 0) x = -x;
-                const double wv = x < 1.0 ? 1.0 - x : 0.0;
-                ws[i].push_back(wv);
-                total += wv;
-            }
-            if (total != 0.0)
-                for (double &v : ws[i]) v /= total;
-            ln[i] = make_int2((int)xmin, (int)ws[i].size());
-        } else {
-            double f = scale * (i + 0.5) - 0.5;
-            if (f < 0.0) f = 0.0;
-            int i0 = (int)f;
-            if (i0 > n_in - 1) i0 = n_in - 1;
-            const int i1 = i0 + (i0 < n_in - 1 ? 1 : 0);
-            const double l1 = f - i0;
-            if (i1 == i0) ws[i] = {1.0};              // (1-l)*p + l*p
-            else ws[i] = {1.0 - l1, l1};
-            ln[i] = make_int2(i0, (int)ws[i].size());
-        }
-        maxt = std::max(maxt, (int)ws[i].size());
-    }
-    maxt = tap_bucket(maxt);                          // zero-padded to the kernels' compile-time bounds
-    w.assign((size_t)n_out * maxt, 0.f);
-    for (int i = 0; i < n_out; ++i)
-        for (size_t k = 0; k < ws[i].size(); ++k) w[(size_t)i * maxt + k] = (float)ws[i][k];
-}
-
-size_t per2_tables(const agx_config &c) {
-    std::vector<int2> ln;
-    std::vector<float> w;
-    int m1 = 0, m3 = 0;
-    axis_taps(c.obs_h, c.per_h, c.antialias != 0, ln, w, m1);
-    axis_taps(c.per_h, c.obs_h, c.antialias != 0, ln, w, m3);
-    return (size_t)c.per_h * (sizeof(int2) + m1 * sizeof(float)) + (size_t)c.obs_h * (sizeof(int2) + m3 * sizeof(float));
-}
-
-size_t per2_lds(const agx_config &c) {
-    const size_t raw = ((size_t)c.obs_h * c.obs_w + 15) & ~(size_t)15;
-    // A[oh][pw] and C[ph][ow] share one region (C is written after A's last read), then B[ph][pw]
-    const size_t ac = (std::max((size_t)c.obs_h * c.per_w, (size_t)c.per_h * c.obs_w) + 3) & ~(size_t)3;
-    const size_t b = ((size_t)c.per_h * c.per_w + 3) & ~(size_t)3;
-    // + the pass-1 and pass-3 tap tables ({lo,n} + zero-padded weights; bounded by the bucketed tap counts,
-    //   which per2_tables() below computes the same way agx_create does)
-    return 1024 + raw + (ac + b) * sizeof(float) + per2_tables(c);
-}
-
-// K4: one family = the taps of every window size r in [1, rmax] along one axis.
-//   which = 0: r -> fov (squeeze)   1: fov -> r (expand back)   2: r -> obs (final resize)
-struct HostFamily {
-    std::vector<int2> ln;
-    std::vector<float> w;
-    std::vector<int4> meta;                       // [rmax + 1]
-    std::vector<size_t> floats;                   // LDS floats of the staged table of size r
-};
-HostFamily build_family(int which, int rmax, int fov, int obs, bool antialias) {
-    HostFamily f;
-    f.meta.assign(rmax + 1, make_int4(0, 0, 1, 0));
-    f.floats.assign(rmax + 1, 0);
-    for (int r = 1; r <= rmax; ++r) {
-        std::vector<int2> ln;
-        std::vector<float> w;
-        int maxt = 0;
-        const int n_in = which == 0 ? r : (which == 1 ? fov : r);
-        const int n_out = which == 0 ? fov : (which == 1 ? r : obs);
-        axis_taps(n_in, n_out, antialias, ln, w, maxt);
-        f.meta[r] = make_int4((int)f.ln.size(), (int)f.w.size(), maxt, n_out);
-        f.floats[r] = (((size_t)2 * n_out + (size_t)n_out * maxt) + 3) & ~(size_t)3;
-        f.ln.insert(f.ln.end(), ln.begin(), ln.end());
-        f.w.insert(f.w.end(), w.begin(), w.end());
-    }
-    return f;
-}
-
-size_t flex2_lds(const agx_config &c, size_t tab_floats) {
-    const size_t raw = ((size_t)c.obs_h * c.obs_w + 15) & ~(size_t)15;
-    const size_t ae = (std::max((size_t)c.obs_h * c.fov_w, (size_t)c.fov_h * c.obs_w) + 3) & ~(size_t)3;
-    const size_t b = ((size_t)c.fov_h * c.fov_w + 3) & ~(size_t)3;
-    const size_t cc = ((size_t)c.fov_h * c.obs_w + 3) & ~(size_t)3;      // C aliases the raw frame bytes
-    return 1024 + std::max(raw, cc * sizeof(float)) + (ae + b + tab_floats) * sizeof(float);
-}
-
 template <class T>
 int upload(agx_ctx *ctx, T **dptr, const std::vector<T> &h) {
     AGX_HIP(ctx, hipMalloc(reinterpret_cast<void **>(dptr), h.size() * sizeof(T)));
@@ -292,41 +183,35 @@ template <class F>
 int with_planes(int planes, F &&f) {
     return planes == 3 ? f(std::integral_constant<int, 3>{}) : f(std::integral_constant<int, 1>{});
 }
+// Calls f(g) with the geometry argument a plan selects: the compile-time GeomS<84, 84, 30, 30> (K2, K4, K5, K6) /
+// PGeomS<84, 84, 30, 30, 20, 20> (K3) where `headline`, the run-time one otherwise.
+template <class F>
+int with_geom(bool headline, const GeomR &gr, F &&f) {
+    return headline ? f(GeomS<84, 84, 30, 30>{}) : f(gr);
+}
+template <class F>
+int with_pgeom(bool headline, const PGeomR &pg, F &&f) {
+    return headline ? f(PGeomS<84, 84, 30, 30, 20, 20>{}) : f(pg);
+}
+// Calls f(std::integral_constant<int, MODE>{}) with the AGX_OUT_* mode of a fixed-fovea kernel (K2, K5)
+template <class F>
+int with_mode(int mode, F &&f) {
+    switch (mode) {
+        case AGX_OUT_RAW: return f(std::integral_constant<int, AGX_OUT_RAW>{});
+        case AGX_OUT_MASK: return f(std::integral_constant<int, AGX_OUT_MASK>{});
+        default: return f(std::integral_constant<int, AGX_OUT_RESIZE>{});
+    }
+}
+GeomR geom_r(const agx_config &c) { return GeomR{c.obs_h, c.obs_w, c.fov_h, c.fov_w}; }
 int obs_elem_bytes(int t) { return t == AGX_OBS_F32 ? 4 : 2; }
-
-// the compile-time geometry of the fixed fovea's kernels (K2, K5, K6: GeomS<84, 84, 30, 30>)
-bool headline_fixed(const agx_config &c) { return c.obs_h == 84 && c.obs_w == 84 && c.fov_h == 30 && c.fov_w == 30; }
-
-size_t fixed_lds(const agx_config &c) {
-    // window rows u8 [fh][ow] (16-B padded) | ytab[oh] | H[fh][ow]   (agx_fixed_phases.h: fixed_carve)
-    size_t b = (size_t)agx::fixed_pad(c.fov_h, c.obs_w);
-    if (c.out_mode == AGX_OUT_RESIZE) b += (size_t)c.obs_h * sizeof(Tap) + (size_t)c.fov_h * c.obs_w * sizeof(float);
-    return b;
+// bytes of one env's observation in the context's element type: frame_stack * planes images, fov-sized where `crop` (the row of
+// agx_obs_shape: crop = a fixed fovea in raw-crop mode)
+size_t obs_row_bytes(const agx_ctx *ctx, bool crop) {
+    const agx_config &c = ctx->cfg;
+    return (size_t)c.frame_stack * ctx->planes * (crop ? (size_t)c.fov_h * c.fov_w : (size_t)c.obs_h * c.obs_w) * obs_elem_bytes(ctx->obs_type);
 }
-#ifdef AGX_EXPERIMENTS
-size_t fixed2_lds(const agx_config &c) {     // k_fovea_fixed2: lut[256] f32 | raw frame u8 (16-B padded) | ytab[oh] | H[fh][ow]
-    const size_t raw = ((size_t)c.obs_h * c.obs_w + 15) & ~(size_t)15;
-    return 1024 + raw + (size_t)c.obs_h * sizeof(Tap) + (size_t)c.fov_h * c.obs_w * sizeof(float);
-}
-#endif
-
-// second LDS buffer of the generic kernels, in floats: flexible ping-pongs two full frames,
-// peripheral keeps A[oh][pw] | B[ph][pw] | C[ph][ow] there
-size_t generic_buf1(const agx_config &c) {
-    const size_t cap = ((size_t)c.obs_h * c.obs_w + 3) & ~(size_t)3;
-    if (c.kind != AGX_KIND_PERIPHERAL) return cap;
-    const size_t abc = (size_t)c.obs_h * c.per_w + (size_t)c.per_h * c.per_w + (size_t)c.per_h * c.obs_w;
-    return (abc + 3) & ~(size_t)3;
-}
-
-size_t generic_lds(const agx_config &c) {
-    const size_t cap = ((size_t)c.obs_h * c.obs_w + 3) & ~(size_t)3;
-    int tmax = std::max(std::max(c.obs_h, c.obs_w), std::max(c.fov_h, c.fov_w));
-    if (c.kind == AGX_KIND_PERIPHERAL) tmax = std::max(tmax, std::max(c.per_h, c.per_w));
-    return (cap + generic_buf1(c)) * sizeof(float) + (size_t)tmax * sizeof(Tap);
-}
-
-constexpr size_t kMaxLds = 160 * 1024;   // gfx950: a workgroup may take the whole 160 KiB of its CU
+// bytes of one env's sensory action (two values) at action dtype `dt`
+size_t action_stride(int dt) { return dt == AGX_DT_F64 || dt == AGX_DT_I64 ? 16 : 8; }
 
 // ---- env range (agx_env_range, include/agx_hostout.h; agx_range.h says how it reaches the kernels)
 bool full_range(const agx_ctx *ctx) { return ctx->rng_lo == 0 && ctx->rng_n == ctx->cfg.num_envs; }
@@ -356,7 +241,154 @@ void ingest_range(const agx_ctx *ctx, P &p, const uint8_t *P::*frames, size_t en
     p.head_out += lo;
 }
 
+// ---- K1: what every ingest entry point shares
+// the entry points that do not run on a colour (AGX_FRAME_RGB) context: the raw-screen Atari ingests, the fused Atari step and
+// the packed ragged crops
+int refuse_rgb(agx_ctx *ctx, const char *who) {
+    return fail(ctx, AGX_E_STATE, "%s: not valid on an AGX_FRAME_RGB context (colour frames come in through agx_ingest_rgb with "
+                "AGX_GRAY_NONE)", who);
+}
+
+// the launch arguments of the K1 band kernels for one screen layout, at the band height its plan holds
+IngestParams ingest_params(agx_ctx *ctx, const uint8_t *d_frames, const uint8_t *d_cmd, int layout = kK1Rgb) {
+    const agx_config &c = ctx->cfg;
+    const bool compact = layout >= kK1RgbCompact;
+    IngestParams p;
+    p.frames = d_frames;
+    p.cmd = d_cmd;
+    p.ring = ctx->ring;
+    p.head_in = ctx->head[ctx->cur_head];
+    p.head_out = ctx->head[ctx->cur_head ^ 1];
+    p.xtab = ctx->in_xtab;
+    p.ytab = compact ? ctx->in_ytab_c : ctx->in_ytab;     // compact screens: packed row indices
+    p.oh = c.obs_h;
+    p.ow = c.obs_w;
+    p.fs = c.frame_stack;
+    p.band_rows = ctx->k1l[layout].band_rows;
+    p.y_affine = compact ? 0 : ctx->k1.y_affine;
+    p.y_mul = ctx->k1.y_mul;
+    p.y_add = ctx->k1.y_add;
+    p.y_shift = ctx->k1.y_shift;
+    p.nbands = ctx->k1l[layout].nbands;
+    p.xtab12 = ctx->in_xtab12;
+    p.ytab12 = ctx->in_ytab12;
+    p.ow4_inv16 = (65536 + c.obs_w / 4 - 1) / (c.obs_w / 4);
+    p.src_rows = compact ? (int32_t)ctx->src_rows.size() : 0;
+    p.stamps = nullptr;
+#ifdef AGX_STAMPS
+    if (const char *e = getenv("AGX_DBG_PTR")) p.stamps = reinterpret_cast<unsigned long long *>(strtoull(e, nullptr, 0));
+#endif
+    return p;
+}
+// after a ranged ingest launch, in front of the head flip
+void ingest_carry(const agx_ctx *ctx, void *stream) {
+    range_carry(ctx, ctx->head[ctx->cur_head], ctx->head[ctx->cur_head ^ 1], nullptr, nullptr, 1, S(stream));
+}
+
+// ---- K2 / K3 / K4: what every fovea entry point shares
+int check_dt(agx_ctx *ctx, const void *d_action, int dt) {
+    if (d_action && (dt < AGX_DT_F32 || dt > AGX_DT_I64)) return fail(ctx, AGX_E_INVALID, "unknown action dtype %d", dt);
+    return AGX_OK;
+}
+
+FovParams fov_params(agx_ctx *ctx, const void *d_action, int dt, const int32_t *d_type, const uint8_t *d_mask,
+                            float *d_obs, int32_t *d_loc, int32_t *d_res) {
+    const agx_config &c = ctx->cfg;
+    FovParams p;
+    p.ring = ctx->ring;
+    p.head = ctx->head[ctx->cur_head];
+    p.loc_in = ctx->loc[ctx->cur_fov];
+    p.loc_out = ctx->loc[ctx->cur_fov ^ 1];
+    p.res_in = ctx->res[ctx->cur_fov];
+    p.res_out = ctx->res[ctx->cur_fov ^ 1];
+    p.action = d_action;
+    p.action_type = d_type;
+    p.mask = d_mask;
+    p.obs = d_obs;
+    p.user_loc = d_loc;
+    p.user_res = d_res;
+    p.xtab = ctx->fx_xtab;
+    p.ytab = ctx->fx_ytab;
+    p.sas_lo = c.sas_lo;
+    p.sas_hi = c.sas_hi;
+    p.action_dt = dt;
+    p.relative = c.action_mode == AGX_MODE_RELATIVE;
+    p.fs = c.frame_stack;
+    p.out_mode = c.out_mode;
+    p.antialias = c.antialias != 0;
+    p.per_h = c.per_h;
+    p.per_w = c.per_w;
+    p.buf1_floats = (int32_t)generic_buf1(c);
+    p.cmd = nullptr;
+    p.phase = 0;
+    p.packed = nullptr;
+    p.packed_off = nullptr;
+    p.packed_cap = 0;
+    p.stamps = nullptr;
+#ifdef AGX_STAMPS
+    if (const char *e = getenv("AGX_DBG_PTR2")) p.stamps = reinterpret_cast<unsigned long long *>(strtoull(e, nullptr, 0));
+#endif
+    return p;
+}
+// the context's env range on a fovea launch: every per-env base pointer advanced by rng_lo envs (the grid's env dimension is
+// rng_n); the observation row is that of agx_obs_shape in the context's element type
+void fov_range(const agx_ctx *ctx, FovParams &p) {
+    const size_t lo = (size_t)ctx->rng_lo;
+    if (lo == 0) return;
+    const agx_config &c = ctx->cfg;
+    const size_t planes = (size_t)c.frame_stack * ctx->planes, px = (size_t)c.obs_h * c.obs_w;
+    p.ring += lo * planes * px;
+    p.head += lo;
+    p.loc_in += 2 * lo;
+    p.loc_out += 2 * lo;
+    p.res_in += 2 * lo;
+    p.res_out += 2 * lo;
+    if (p.action) p.action = static_cast<const char *>(p.action) + lo * action_stride(p.action_dt);
+    if (p.action_type) p.action_type += lo;
+    if (p.mask) p.mask += lo;
+    p.obs = reinterpret_cast<float *>(reinterpret_cast<char *>(p.obs) + lo * obs_row_bytes(ctx, c.kind == AGX_KIND_FIXED && c.out_mode == AGX_OUT_RAW));
+    if (p.user_loc) p.user_loc += 2 * lo;
+    if (p.user_res) p.user_res += 2 * lo;
+}
+// after a ranged fovea launch, in front of the fov flip: fov_loc of the out-of-range envs, and fov_res where the kind writes it
+void fov_carry(const agx_ctx *ctx, void *stream) {
+    const bool flex = ctx->cfg.kind == AGX_KIND_FLEXIBLE;
+    range_carry(ctx, ctx->loc[ctx->cur_fov], ctx->loc[ctx->cur_fov ^ 1], flex ? ctx->res[ctx->cur_fov] : nullptr,
+                flex ? ctx->res[ctx->cur_fov ^ 1] : nullptr, 2, S(stream));
+}
+
+// the state / scan launch of the packed form (fov_env.py:300-324 + level 1 of the exclusive scan of the crop sizes; the scratch
+// belongs to the context since agx_create)
+FlexParams flex_params(const agx_ctx *ctx) {       // k_fovea_flexible2's table families
+    const agx_config &c = ctx->cfg;
+    FlexParams g;
+    TabFamily *fam[6] = {&g.wd, &g.wb, &g.wf, &g.hd, &g.hb, &g.hf};
+    for (int k = 0; k < 6; ++k) {
+        fam[k]->ln = ctx->flex_ln[k];
+        fam[k]->w = ctx->flex_w[k];
+        fam[k]->meta = ctx->flex_meta[k];
+    }
+    g.oh = c.obs_h; g.ow = c.obs_w; g.fh = c.fov_h; g.fw = c.fov_w;
+    return g;
+}
+
+FlexScanParams packed_scan_params(agx_ctx *ctx, const void *d_action, int action_dtype, const int32_t *d_action_type,
+                                         int32_t *d_fov_loc, int32_t *d_fov_res) {
+    FlexScanParams q;
+    q.f = fov_params(ctx, d_action, action_dtype, d_action_type, nullptr, nullptr, d_fov_loc, d_fov_res);
+    q.local_off = ctx->pack_local;
+    q.block_tot = ctx->pack_block;
+    q.n = ctx->cfg.num_envs;
+    q.oh = ctx->cfg.obs_h;
+    q.ow = ctx->cfg.obs_w;
+    return q;
+}
+
 }  // namespace
+
+#ifdef AGX_EXPERIMENTS
+#include "experiments/agx_experiments_host.h"   // the opt-in launch forms the entry points below hook (exp_*)
+#endif
 
 extern "C" {
 
@@ -428,6 +460,12 @@ int agx_create(const agx_config *cfg, agx_ctx **out) {
     agx_config c_split = *cfg;
     c_split.out_mode = cfg->out_mode & ~(AGX_OBS_TYPE_MASK | AGX_FRAME_RGB);
     const agx_config &c = c_split;
+    agx_ctx::Tune tune;          // the knobs: read here, once per context
+    tune.generic = env_int("AGX_FOVEA_GENERIC");
+    tune.no_full = env_int("AGX_INGEST_NO_FULL");
+    tune.flex_v2 = env_int("AGX_FLEX_V2");
+    tune.per_v2 = env_int("AGX_PER_V2");
+    tune.packed_unfused = env_int("AGX_STEP_PACKED_UNFUSED");
     if (c.num_envs < 1 || c.num_envs > 65535)   // env index rides on gridDim.y / gridDim.z
         return fail(nullptr, AGX_E_INVALID, "num_envs must be in [1, 65535] per context (shard larger batches)");
     if (c.raw_h != kRawH || c.raw_w != kRawW)
@@ -451,11 +489,7 @@ int agx_create(const agx_config *cfg, agx_ctx **out) {
             return fail(nullptr, AGX_E_INVALID, "fov_init_loc must be finite");
         if (c.kind == AGX_KIND_PERIPHERAL && (c.per_h < 1 || c.per_w < 1 || c.per_h > 1024 || c.per_w > 1024))
             return fail(nullptr, AGX_E_INVALID, "peripheral_res (%d,%d) out of range", c.per_h, c.per_w);
-        // the LDS of the kernel that will actually run: the tuned peripheral kernel when its plan fits (and the
-        // testing knob does not force the fallback), otherwise the generic one
-        const bool per_tuned = env_int("AGX_FOVEA_GENERIC") == 0 && per2_lds(c) <= kMaxLds && c.per_w <= kThreads;
-        const size_t lds = c.kind == AGX_KIND_FIXED ? fixed_lds(c)
-                           : (c.kind == AGX_KIND_PERIPHERAL && per_tuned ? per2_lds(c) : generic_lds(c));
+        const size_t lds = create_lds(c, tune);
         if (lds > kMaxLds)
             return fail(nullptr, AGX_E_INVALID, "geometry needs %zu B of LDS per workgroup (limit %zu)", lds, kMaxLds);
     }
@@ -470,11 +504,8 @@ int agx_create(const agx_config *cfg, agx_ctx **out) {
     ctx->obs_type = obs_type;
     ctx->planes = planes;
     ctx->rng_n = c.num_envs;
-    ctx->tune.generic = env_int("AGX_FOVEA_GENERIC");
-    ctx->tune.no_full = env_int("AGX_INGEST_NO_FULL");
-    ctx->tune.flex_v2 = env_int("AGX_FLEX_V2");
-    ctx->tune.per_v2 = env_int("AGX_PER_V2");
-    ctx->tune.packed_unfused = env_int("AGX_STEP_PACKED_UNFUSED");
+    ctx->tune = tune;
+    ctx->plan = plan_base(c);
 #ifdef AGX_EXPERIMENTS
     ctx->tune.ingest_t = env_int("AGX_INGEST_T");
     ctx->tune.band_rows = env_int("AGX_INGEST_BAND_ROWS");
@@ -541,6 +572,11 @@ int agx_create(const agx_config *cfg, agx_ctx **out) {
         ctx->band_rows = k1_band_rows(c.obs_w, ctx->ingest_t);
         const int forced_br = ctx->tune.band_rows;
         if (forced_br >= 1 && forced_br <= ctx->band_rows) ctx->band_rows = forced_br;
+        // agx_ingest_gray_raw: the plan's 256-thread bands (AGX_INGEST_BAND_ROWS of the experiments build narrows them as it
+        // does the RGB ingest's; the other opt-in variants are RGB-only); compact screens: always the default 256-thread band form
+        const int gray_rows = ctx->ingest_t == 256 ? std::min(k1.plan.band_rows, ctx->band_rows) : k1.plan.band_rows;
+        const int rows[4] = {ctx->band_rows, gray_rows, k1.plan.band_rows, k1.plan.band_rows};
+        for (int k = 0; k < 4; ++k) ctx->k1l[k] = plan_k1(k1.plan, k, rows[k], c.obs_h, c.obs_w, tune);
     }
     if (has_fovea(c)) {
         // _init_fov_loc: np.rint(fov_init_loc).astype(np.int32)  (not clipped)   fov_env.py:149-150
@@ -563,22 +599,16 @@ int agx_create(const agx_config *cfg, agx_ctx **out) {
             if ((rc = upload(ctx, &ctx->res[b], res)) != AGX_OK) return bail(rc);
         }
         if (c.kind == AGX_KIND_FLEXIBLE) {
-            size_t worst_w = 0, worst_h = 0;
             HostFamily fam[6];
+            const size_t tab_floats = build_families(c, fam);   // worst-case LDS floats of the staged tables
             for (int k = 0; k < 6; ++k) {
-                const bool is_w = k < 3;
-                fam[k] = build_family(k % 3, is_w ? c.obs_w : c.obs_h, is_w ? c.fov_w : c.fov_h, is_w ? c.obs_w : c.obs_h,
-                                      c.antialias != 0);
                 if ((rc = upload(ctx, &ctx->flex_ln[k], fam[k].ln)) != AGX_OK) return bail(rc);
                 if ((rc = upload(ctx, &ctx->flex_w[k], fam[k].w)) != AGX_OK) return bail(rc);
                 if ((rc = upload(ctx, &ctx->flex_meta[k], fam[k].meta)) != AGX_OK) return bail(rc);
             }
-            for (int r = 1; r <= c.obs_w; ++r) worst_w = std::max(worst_w, fam[0].floats[r] + fam[1].floats[r] + fam[2].floats[r]);
-            for (int r = 1; r <= c.obs_h; ++r) worst_h = std::max(worst_h, fam[3].floats[r] + fam[4].floats[r] + fam[5].floats[r]);
-            ctx->flex_tab_floats = worst_w + worst_h;
             // resize_to_full: the composed-operator kernel where its plan applies (thread-per-column, <= 16 taps)
             const Flex3Host f3 = build_flex3(c);
-            if (f3.ok && flex3_lds(f3, c) <= kMaxLds) {
+            if (flex3_fits(f3, c)) {
                 Flex3Params &q = ctx->f3;
                 if ((rc = upload_owned(ctx, &q.wf, f3.wf)) != AGX_OK) return bail(rc);
                 if ((rc = upload_owned(ctx, &q.wc_meta, f3.wc_meta)) != AGX_OK) return bail(rc);
@@ -591,11 +621,10 @@ int agx_create(const agx_config *cfg, agx_ctx **out) {
                 q.r0_bytes = f3.r0_bytes;
                 q.r1_bytes = f3.r1_bytes;
                 q.dp = f3.dp;
-                ctx->f3_ok = true;
             }
             // raw-crop / mask-out: the composed squeeze-and-back form where its plan applies
             const FlexRawHost fr = build_flexraw(c);
-            if (fr.ok && fr.lds(c) <= kMaxLds) {
+            if (flexraw_fits(fr, c)) {
                 FlexRawParams &q = ctx->fr;
                 if ((rc = upload_owned(ctx, &q.wb_meta, fr.wb_meta)) != AGX_OK) return bail(rc);
                 if ((rc = upload_owned(ctx, &q.wb_lo, fr.wb_lo)) != AGX_OK) return bail(rc);
@@ -608,9 +637,8 @@ int agx_create(const agx_config *cfg, agx_ctx **out) {
                 q.r1_bytes = fr.r1_bytes;
                 q.dp = fr.dp;
                 q.n_envs = c.num_envs;
-                ctx->fr_lds = fr.lds(c);
-                ctx->fr_ok = true;
             }
+            ctx->plan = plan_flexible(c, tune, f3, fr, tab_floats);
             if (c.out_mode == AGX_OUT_RAW) {       // the packed form's scan buffers
                 const size_t nb = (N + kScanEnvsPerBlock - 1) / kScanEnvsPerBlock;
                 TRY(hipMalloc(reinterpret_cast<void **>(&ctx->pack_local), N * sizeof(int64_t)));
@@ -620,8 +648,8 @@ int agx_create(const agx_config *cfg, agx_ctx **out) {
             }
         }
         if (c.kind == AGX_KIND_PERIPHERAL) {
-            const int nin[4] = {c.obs_w, c.obs_h, c.per_w, c.per_h};
-            const int nout[4] = {c.per_w, c.per_h, c.obs_w, c.obs_h};
+            int nin[4], nout[4];
+            per_axes(c, nin, nout);
             for (int k = 0; k < 4; ++k) {
                 std::vector<int2> ln;
                 std::vector<float> w;
@@ -631,10 +659,8 @@ int agx_create(const agx_config *cfg, agx_ctx **out) {
                 if ((rc = upload(ctx, &ctx->per_ln[k], ln)) != AGX_OK) return bail(rc);
                 if ((rc = upload(ctx, &ctx->per_w[k], w)) != AGX_OK) return bail(rc);
             }
-        }
-        if (c.kind == AGX_KIND_PERIPHERAL) {
             const Per3Host h3 = build_per3(c);
-            if (h3.ok && h3.lds <= kMaxLds) {
+            if (per3_fits(h3)) {
                 Per3Params &q = ctx->p3;
                 if ((rc = upload_owned(ctx, &q.lo0, h3.lo0)) != AGX_OK) return bail(rc);
                 if ((rc = upload_owned(ctx, &q.w0, h3.w0)) != AGX_OK) return bail(rc);
@@ -642,11 +668,11 @@ int agx_create(const agx_config *cfg, agx_ctx **out) {
                 if ((rc = upload_owned(ctx, &q.w1, h3.w1)) != AGX_OK) return bail(rc);
                 if ((rc = upload_owned(ctx, &q.x2, h3.x2)) != AGX_OK) return bail(rc);
                 if ((rc = upload_owned(ctx, &q.y3, h3.y3)) != AGX_OK) return bail(rc);
-                q.same = (c.per_h == c.obs_h && c.per_w == c.obs_w) ? 1 : 0;
-                ctx->p3_mt = h3.mt;
-                ctx->p3_lds = h3.lds;
             }
+            ctx->plan = plan_peripheral(c, tune, h3, ctx->per_maxt);
+            ctx->p3.same = ctx->plan.same;
         }
+        if (c.kind == AGX_KIND_FIXED) ctx->plan = plan_fixed(c);
         if (c.kind == AGX_KIND_FIXED && c.out_mode == AGX_OUT_RESIZE) {
             std::vector<Tap> xt(c.obs_w), yt(c.obs_h);
             for (int i = 0; i < c.obs_w; ++i) xt[i] = make_tap_lin2(i, c.fov_w, c.obs_w);
@@ -711,60 +737,6 @@ int64_t agx_algorithmic_bytes(const agx_ctx *ctx, int kernel_id) {
 }
 
 // ---------------------------------------------------------------- K1
-// the entry points that do not run on a colour (AGX_FRAME_RGB) context: the raw-screen Atari ingests, the fused Atari step and
-// the packed ragged crops
-static int refuse_rgb(agx_ctx *ctx, const char *who) {
-    return fail(ctx, AGX_E_STATE, "%s: not valid on an AGX_FRAME_RGB context (colour frames come in through agx_ingest_rgb with "
-                "AGX_GRAY_NONE)", who);
-}
-
-static IngestParams ingest_params(agx_ctx *ctx, const uint8_t *d_frames, const uint8_t *d_cmd) {
-    const agx_config &c = ctx->cfg;
-    IngestParams p;
-    p.frames = d_frames;
-    p.cmd = d_cmd;
-    p.ring = ctx->ring;
-    p.head_in = ctx->head[ctx->cur_head];
-    p.head_out = ctx->head[ctx->cur_head ^ 1];
-    p.xtab = ctx->in_xtab;
-    p.ytab = ctx->in_ytab;
-    p.oh = c.obs_h;
-    p.ow = c.obs_w;
-    p.fs = c.frame_stack;
-    p.band_rows = ctx->band_rows;
-    p.y_affine = ctx->k1.y_affine;
-    p.y_mul = ctx->k1.y_mul;
-    p.y_add = ctx->k1.y_add;
-    p.y_shift = ctx->k1.y_shift;
-    p.nbands = (c.obs_h + ctx->band_rows - 1) / ctx->band_rows;
-    p.xtab12 = ctx->in_xtab12;
-    p.ytab12 = ctx->in_ytab12;
-    p.ow4_inv16 = (65536 + c.obs_w / 4 - 1) / (c.obs_w / 4);
-    p.src_rows = 0;
-    p.stamps = nullptr;
-#ifdef AGX_STAMPS
-    if (const char *e = getenv("AGX_DBG_PTR")) p.stamps = reinterpret_cast<unsigned long long *>(strtoull(e, nullptr, 0));
-#endif
-    return p;
-}
-// after a ranged ingest launch, in front of the head flip
-static void ingest_carry(const agx_ctx *ctx, void *stream) {
-    range_carry(ctx, ctx->head[ctx->cur_head], ctx->head[ctx->cur_head ^ 1], nullptr, nullptr, 1, S(stream));
-}
-
-// agx_ingest_gray_raw: the plan's 256-thread bands (AGX_INGEST_BAND_ROWS of the experiments build narrows them as it does the
-// RGB ingest's; the other opt-in variants are RGB-only)
-static int gray_band_rows(const agx_ctx *ctx) {
-    return ctx->ingest_t == 256 ? std::min(ctx->k1.band_rows, ctx->band_rows) : ctx->k1.band_rows;
-}
-
-static size_t ingest_lds(const agx_ctx *ctx) {
-    return sizeof(int4) * ctx->band_rows + sizeof(int2) * ctx->cfg.obs_w + (size_t)2 * ctx->band_rows * 2 * kRawW;
-}
-// + 8 bytes of slack: phase 2 reads the two ALIGNED dwords around every tap pair, and for the last pair of a row (x0 = 158 at
-// 160 -> 84) the second dword lies past the row's 320 bytes - past the allocation for the very last row (its value is shifted
-// out, but the read must stay inside the workgroup's LDS)
-static size_t band12_lds(const agx_ctx *ctx) { return sizeof(int2) * (kB12Rows + ctx->cfg.obs_w) + kB12GrayB + 8; }
 
 int agx_ingest(agx_ctx *ctx, const uint8_t *d_frames, const uint8_t *d_cmd, void *stream) {
     if (!ctx) return AGX_E_INVALID;
@@ -778,44 +750,16 @@ int agx_ingest(agx_ctx *ctx, const uint8_t *d_frames, const uint8_t *d_cmd, void
     DeviceGuard g(c.device);
     IngestParams p = ingest_params(ctx, d_frames, d_cmd);
     ingest_range(ctx, p, &IngestParams::frames, (size_t)2 * kRawFrameBytes);
-    const int en = ctx->rng_n;             // envs of the launch (num_envs unless agx_env_range narrowed it)
-    const int bands = p.nbands;
-    const size_t lds = ingest_lds(ctx);
+    const K1Launch &l = ctx->k1l[kK1Rgb];
+    const dim3 grid(l.nbands, ctx->rng_n);     // rng_n: the envs of the launch (num_envs unless agx_env_range narrowed it)
 #ifdef AGX_EXPERIMENTS
-    bool launched = true;
-    const int pipe_parts = ctx->tune.pipe_parts;
-    // wave-private form: needs the affine row form, band_rows = 4 * RPW with RPW * ow/4 <= 64 lanes and
-    // 2 frames * RPW rows * 40 pieces <= 240 (RPW <= 3)
-    // (measured equal to the barrier form at N=1024 - 46.5 vs 45.6 us - so it is opt-in: AGX_INGEST_WAVE=1)
-    const bool want_wave = ctx->tune.wave != 0;
-    const int rpw = ctx->band_rows / 4;
-    const bool wave_ok = want_wave && pipe_parts == 0 && ctx->ingest_t == 256 && ctx->k1.y_affine && ctx->band_rows % 4 == 0 &&
-                         rpw >= 1 && rpw <= 3 && rpw * (c.obs_w / 4) <= 64;
-    if (wave_ok) {
-        const size_t slice = ((sizeof(int2) * c.obs_w + (size_t)2 * rpw * kRawW * 2) + 15) & ~(size_t)15;
-        hipLaunchKernelGGL(k_ingest_wave, dim3(bands, en), dim3(256), 4 * slice, S(stream), p);
-    } else if (pipe_parts > 0 && ctx->ingest_t == 256) {
-        const int parts = std::min(pipe_parts, bands);
-        const size_t lds2 = sizeof(int4) * c.obs_h + sizeof(int2) * c.obs_w + (size_t)2 * (2 * ctx->band_rows * 2 * kRawW);
-        hipLaunchKernelGGL(k_ingest_pipe<256>, dim3(parts, en), dim3(256), lds2, S(stream), p);
-    } else if (ctx->ingest_t == 128)
-        hipLaunchKernelGGL(k_ingest<128>, dim3(bands, en), dim3(128), lds, S(stream), p);
-    // (same box, N=1024: 37.5-37.9 us against 37.9-38.2 for the one-band form - K1 is VALU-issue- and HBM-limited, not
-    //  limited by the load-free tail of a workgroup - so it stays opt-in)
-    else if (ctx->tune.no_full == 0 && ctx->tune.pair12 != 0 && ctx->tune.band_rows == 0 && ctx->tune.ingest_t == 0 &&
-             ctx->k1.y_affine && ctx->band_rows == 12 && c.obs_h % 12 == 0 && (c.obs_w / 4) * 12 <= kThreads)
-        AGX_LAUNCH(0, k_ingest_pair12, dim3(bands, (en + 1) / 2), dim3(256), lds + (size_t)2 * 12 * 2 * kRawW, S(stream), p,
-                   en);
-    else launched = false;
-    if (!launched)
+    if (!exp_ingest(ctx, p, stream))
 #endif
     {
         // the headline form where its plan applies (12-row bands all full, affine source rows, adjacent x taps), the general
         // band kernel otherwise
-        if (ctx->tune.no_full == 0 && k1_band12(ctx->k1, false, ctx->band_rows))
-            AGX_LAUNCH(0, k_ingest_full12, dim3(bands, en), dim3(256), band12_lds(ctx), S(stream), p);
-        else
-            AGX_LAUNCH(0, k_ingest<256>, dim3(bands, en), dim3(256), lds, S(stream), p);
+        if (l.band12) AGX_LAUNCH(0, k_ingest_full12, grid, dim3(256), l.lds, S(stream), p);
+        else AGX_LAUNCH(0, k_ingest<256>, grid, dim3(256), l.lds, S(stream), p);
     }
     ingest_carry(ctx, stream);
     AGX_HIP(ctx, hipGetLastError());
@@ -831,15 +775,12 @@ int agx_ingest_gray_raw(agx_ctx *ctx, const uint8_t *d_gray, const uint8_t *d_cm
     if (c.obs_h != c.obs_w)
         return fail(ctx, AGX_E_STATE, "agx_ingest_gray_raw needs a square obs_size (cv2.resize takes (width, height): atari_env.py:74)");
     DeviceGuard g(c.device);
-    IngestParams p = ingest_params(ctx, d_gray, d_cmd);
+    IngestParams p = ingest_params(ctx, d_gray, d_cmd, kK1Gray);
     ingest_range(ctx, p, &IngestParams::frames, (size_t)2 * kRawH * kRawW);
-    p.band_rows = gray_band_rows(ctx);
-    p.nbands = (c.obs_h + p.band_rows - 1) / p.band_rows;
-    const size_t lds = sizeof(int4) * p.band_rows + sizeof(int2) * c.obs_w + (size_t)2 * p.band_rows * 2 * kRawW;
-    if (ctx->tune.no_full == 0 && k1_band12(ctx->k1, false, p.band_rows))
-        AGX_LAUNCH(0, k_ingest_grayraw_full12, dim3(p.nbands, ctx->rng_n), dim3(kThreads), band12_lds(ctx), S(stream), p);
-    else
-        AGX_LAUNCH(0, k_ingest_grayraw, dim3(p.nbands, ctx->rng_n), dim3(kThreads), lds, S(stream), p);
+    const K1Launch &l = ctx->k1l[kK1Gray];
+    const dim3 grid(l.nbands, ctx->rng_n), block(kThreads);
+    if (l.band12) AGX_LAUNCH(0, k_ingest_grayraw_full12, grid, block, l.lds, S(stream), p);
+    else AGX_LAUNCH(0, k_ingest_grayraw, grid, block, l.lds, S(stream), p);
     ingest_carry(ctx, stream);
     AGX_HIP(ctx, hipGetLastError());
     ctx->cur_head ^= 1;
@@ -863,22 +804,17 @@ static int ingest_compact(agx_ctx *ctx, const uint8_t *d_rows, const uint8_t *d_
         return fail(ctx, AGX_E_INVALID, "%s: obs_size (%d,%d) is not square (cv2.resize takes (width, height): atari_env.py:74)", who,
                     c.obs_h, c.obs_w);
     DeviceGuard g(c.device);
-    IngestParams p = ingest_params(ctx, d_rows, d_cmd);
-    p.src_rows = (int32_t)ctx->src_rows.size();
+    const int layout = gray ? kK1GrayCompact : kK1RgbCompact;
+    IngestParams p = ingest_params(ctx, d_rows, d_cmd, layout);
     ingest_range(ctx, p, &IngestParams::frames, (size_t)2 * ctx->src_rows.size() * kRawW * (gray ? 1 : 3));
-    p.ytab = ctx->in_ytab_c;             // packed row indices
-    p.y_affine = 0;
-    const int br = ctx->k1.band_rows;    // always the default 256-thread band form
-    p.band_rows = br;
-    p.nbands = (c.obs_h + br - 1) / br;
-    const size_t lds = sizeof(int4) * br + sizeof(int2) * c.obs_w + (size_t)2 * br * 2 * kRawW;
-    const dim3 grid(p.nbands, ctx->rng_n), block(kThreads);
-    if (ctx->tune.no_full == 0 && k1_band12(ctx->k1, true, br)) {
-        if (gray) AGX_LAUNCH(0, k_ingest_grayraw_full12_compact, grid, block, band12_lds(ctx), S(stream), p);
-        else AGX_LAUNCH(0, k_ingest_full12_compact, grid, block, band12_lds(ctx), S(stream), p);
+    const K1Launch &l = ctx->k1l[layout];
+    const dim3 grid(l.nbands, ctx->rng_n), block(kThreads);
+    if (l.band12) {
+        if (gray) AGX_LAUNCH(0, k_ingest_grayraw_full12_compact, grid, block, l.lds, S(stream), p);
+        else AGX_LAUNCH(0, k_ingest_full12_compact, grid, block, l.lds, S(stream), p);
     } else {
-        if (gray) AGX_LAUNCH(0, k_ingest_grayraw_compact, grid, block, lds, S(stream), p);
-        else AGX_LAUNCH(0, k_ingest_compact, grid, block, lds, S(stream), p);
+        if (gray) AGX_LAUNCH(0, k_ingest_grayraw_compact, grid, block, l.lds, S(stream), p);
+        else AGX_LAUNCH(0, k_ingest_compact, grid, block, l.lds, S(stream), p);
     }
     ingest_carry(ctx, stream);
     AGX_HIP(ctx, hipGetLastError());
@@ -979,7 +915,7 @@ static int stack_launch(agx_ctx *ctx, int which, const uint8_t *in_u8, uint8_t *
         const size_t lo = (size_t)ctx->rng_lo, row = (size_t)c.frame_stack * ctx->planes * c.obs_h * c.obs_w;
         p.ring += lo * row;
         p.head += lo;
-        p.out_f32 = reinterpret_cast<float *>(reinterpret_cast<char *>(out_f32) + lo * row * obs_elem_bytes(ctx->obs_type));
+        p.out_f32 = reinterpret_cast<float *>(reinterpret_cast<char *>(out_f32) + lo * obs_row_bytes(ctx, false));
         en = ctx->rng_n;
     }
     const dim3 grid((p.words + kThreads - 1) / kThreads, c.frame_stack * ctx->planes, en);
@@ -1060,79 +996,6 @@ int agx_set_fov_state(agx_ctx *ctx, const int32_t *d_fov_loc, const int32_t *d_f
 }
 
 // ---------------------------------------------------------------- K2/K3/K4
-static int check_dt(agx_ctx *ctx, const void *d_action, int dt) {
-    if (d_action && (dt < AGX_DT_F32 || dt > AGX_DT_I64)) return fail(ctx, AGX_E_INVALID, "unknown action dtype %d", dt);
-    return AGX_OK;
-}
-
-static FovParams fov_params(agx_ctx *ctx, const void *d_action, int dt, const int32_t *d_type, const uint8_t *d_mask,
-                            float *d_obs, int32_t *d_loc, int32_t *d_res) {
-    const agx_config &c = ctx->cfg;
-    FovParams p;
-    p.ring = ctx->ring;
-    p.head = ctx->head[ctx->cur_head];
-    p.loc_in = ctx->loc[ctx->cur_fov];
-    p.loc_out = ctx->loc[ctx->cur_fov ^ 1];
-    p.res_in = ctx->res[ctx->cur_fov];
-    p.res_out = ctx->res[ctx->cur_fov ^ 1];
-    p.action = d_action;
-    p.action_type = d_type;
-    p.mask = d_mask;
-    p.obs = d_obs;
-    p.user_loc = d_loc;
-    p.user_res = d_res;
-    p.xtab = ctx->fx_xtab;
-    p.ytab = ctx->fx_ytab;
-    p.sas_lo = c.sas_lo;
-    p.sas_hi = c.sas_hi;
-    p.action_dt = dt;
-    p.relative = c.action_mode == AGX_MODE_RELATIVE;
-    p.fs = c.frame_stack;
-    p.out_mode = c.out_mode;
-    p.antialias = c.antialias != 0;
-    p.per_h = c.per_h;
-    p.per_w = c.per_w;
-    p.buf1_floats = (int32_t)generic_buf1(c);
-    p.cmd = nullptr;
-    p.phase = 0;
-    p.packed = nullptr;
-    p.packed_off = nullptr;
-    p.packed_cap = 0;
-    p.stamps = nullptr;
-#ifdef AGX_STAMPS
-    if (const char *e = getenv("AGX_DBG_PTR2")) p.stamps = reinterpret_cast<unsigned long long *>(strtoull(e, nullptr, 0));
-#endif
-    return p;
-}
-// the context's env range on a fovea launch: every per-env base pointer advanced by rng_lo envs (the grid's env dimension is
-// rng_n); the observation row is that of agx_obs_shape in the context's element type
-static void fov_range(const agx_ctx *ctx, FovParams &p) {
-    const size_t lo = (size_t)ctx->rng_lo;
-    if (lo == 0) return;
-    const agx_config &c = ctx->cfg;
-    const size_t planes = (size_t)c.frame_stack * ctx->planes, px = (size_t)c.obs_h * c.obs_w;
-    const bool crop = c.kind == AGX_KIND_FIXED && c.out_mode == AGX_OUT_RAW;
-    const size_t row_bytes = planes * (crop ? (size_t)c.fov_h * c.fov_w : px) * obs_elem_bytes(ctx->obs_type);
-    const bool wide = p.action_dt == AGX_DT_F64 || p.action_dt == AGX_DT_I64;
-    p.ring += lo * planes * px;
-    p.head += lo;
-    p.loc_in += 2 * lo;
-    p.loc_out += 2 * lo;
-    p.res_in += 2 * lo;
-    p.res_out += 2 * lo;
-    if (p.action) p.action = static_cast<const char *>(p.action) + lo * (wide ? 16 : 8);
-    if (p.action_type) p.action_type += lo;
-    if (p.mask) p.mask += lo;
-    p.obs = reinterpret_cast<float *>(reinterpret_cast<char *>(p.obs) + lo * row_bytes);
-    if (p.user_loc) p.user_loc += 2 * lo;
-    if (p.user_res) p.user_res += 2 * lo;
-}
-// after a ranged fovea launch, in front of the fov flip: fov_loc of the out-of-range envs, and fov_res where the kind writes it
-static void fov_carry(const agx_ctx *ctx, void *stream) {
-    const bool flex = ctx->cfg.kind == AGX_KIND_FLEXIBLE;
-    range_carry(ctx, ctx->loc[ctx->cur_fov], ctx->loc[ctx->cur_fov ^ 1], flex ? ctx->res[ctx->cur_fov] : nullptr,
-                flex ? ctx->res[ctx->cur_fov ^ 1] : nullptr, 2, S(stream));
-}
 
 int agx_fovea_fixed(agx_ctx *ctx, const void *d_action, int action_dtype, const uint8_t *d_mask, float *d_obs,
                     int32_t *d_fov_loc, void *stream) {
@@ -1145,43 +1008,21 @@ int agx_fovea_fixed(agx_ctx *ctx, const void *d_action, int action_dtype, const 
     DeviceGuard g(c.device);
     FovParams p = fov_params(ctx, d_action, action_dtype, nullptr, d_mask, d_obs, d_fov_loc, nullptr);
     fov_range(ctx, p);
-    const size_t lds = fixed_lds(c);
-    const bool headline = headline_fixed(c);
-    using GS = GeomS<84, 84, 30, 30>;
-    const GeomR gr{c.obs_h, c.obs_w, c.fov_h, c.fov_w};
     const dim3 grid(c.frame_stack * ctx->planes, ctx->rng_n), block(kThreads);
-#define LAUNCH(MODE)                                                                                     \
-    do {                                                                                                 \
-        if (headline)                                                                                    \
-            AGX_LAUNCH(1, (k_fovea_fixed<GS, MODE, OT, NC>), grid, block, lds, S(stream), GS{}, p);  \
-        else                                                                                             \
-            AGX_LAUNCH(1, (k_fovea_fixed<GeomR, MODE, OT, NC>), grid, block, lds, S(stream), gr, p); \
-    } while (0)
 #ifdef AGX_EXPERIMENTS
-    // two physical slots per workgroup (whole launch resident at once, second frame's load hidden): measured a tie
-    // with the one-slot form at N=1024 (26.3 vs 25.8 us) - the launch is store-limited
-    if (c.out_mode == AGX_OUT_RESIZE && c.frame_stack % 2 == 0 && ctx->tune.pair == 1 && ctx->obs_type == AGX_OBS_F32 &&
-        ctx->planes == 1) {
-        const dim3 grid2(c.frame_stack / 2, ctx->rng_n);
-        if (headline)
-            hipLaunchKernelGGL((k_fovea_fixed2<GS>), grid2, block, fixed2_lds(c), S(stream), GS{}, p);
-        else
-            hipLaunchKernelGGL((k_fovea_fixed2<GeomR>), grid2, block, fixed2_lds(c), S(stream), gr, p);
-    } else
+    if (!exp_fovea_fixed(ctx, p, stream))
 #endif
         with_planes(ctx->planes, [&](auto pc) {
-        constexpr int NC = decltype(pc)::value;
-        return with_obs_type(ctx->obs_type, [&](auto tag) {
-            using OT = decltype(tag);
-            switch (c.out_mode) {
-                case AGX_OUT_RAW: LAUNCH(AGX_OUT_RAW); break;
-                case AGX_OUT_MASK: LAUNCH(AGX_OUT_MASK); break;
-                default: LAUNCH(AGX_OUT_RESIZE); break;
-            }
-            return 0;
+            return with_obs_type(ctx->obs_type, [&](auto tag) {
+                return with_mode(c.out_mode, [&](auto mode) {
+                    return with_geom(ctx->plan.headline, geom_r(c), [&](auto g) {
+                        AGX_LAUNCH(1, (k_fovea_fixed<decltype(g), decltype(mode)::value, decltype(tag), decltype(pc)::value>), grid, block,
+                                   ctx->plan.lds, S(stream), g, p);
+                        return 0;
+                    });
+                });
+            });
         });
-        });
-#undef LAUNCH
     fov_carry(ctx, stream);
     AGX_HIP(ctx, hipGetLastError());
     ctx->cur_fov ^= 1;
@@ -1203,154 +1044,7 @@ int agx_step_fixed(agx_ctx *ctx, const uint8_t *d_frames, const uint8_t *d_cmd, 
     // other forms of this call that were built and measured slower or equal (heterogeneous fused launch + tail, env-range
     // parts on internal streams, one workgroup per env) live in the experiments build only.
 #ifdef AGX_EXPERIMENTS
-    const bool headline = c.obs_h == 84 && c.obs_w == 84 && c.fov_h == 30 && c.fov_w == 30;
-    // The heterogeneous launch (ingest bands + fovea of the untouched slots in one grid, written slot after) is
-    // bit-identical and measured a tie at N=1024 (69.3 vs 67.9 us per step: it fills the ingest's drain but its
-    // second launch is one latency chain long), so the default is the two stand-alone launches.
-    const bool fused = ctx->tune.fused != 0 && ctx->obs_type == AGX_OBS_F32;   // tuning / testing knob (f32 outputs only)
-    // ---- split step: the batch as P env ranges, range 0 on the caller's stream, the others on internal streams forked
-    // from it and joined back before the call returns its work to the caller's stream order.  One range's fovea stores
-    // and ingest drain then run under another range's ingest loads (reads and writes of the same step overlap), with
-    // the results of one launch pair bit for bit (same kernels, disjoint env ranges, no shared state).
-    const agx_ctx::Tune &tn = ctx->tune;
-    // (the forms below write f32 observations only: a 16-bit context takes the product form)
-    const bool default_forms = !fused && !tn.ingest_t && !tn.band_rows && !tn.pipe_parts && !tn.wave && !tn.pair && !tn.no_full &&
-                               ctx->obs_type == AGX_OBS_F32;
-    // Measured at N=1024 (same box, bench.py --steps 600): one launch pair 60.9 us per step; 2 parts 72.7 (69.3 with
-    // low-priority internal streams, 75.1 with high), 3 parts 86.6, 4 parts 105: every cross-stream event edge costs more
-    // than the overlap returns (round 1's +6-10 % came from two independent contexts that never join).  So it is opt-in.
-    int parts = tn.split > 0 ? tn.split : 1;
-    parts = std::min(std::min(parts, 4), c.num_envs);
-    // ---- one launch, one workgroup per env (agx_step_env.h): the headline geometry's resize_to_full path
-    if (tn.step_env != 0 && default_forms && !mid_event && c.out_mode == AGX_OUT_RESIZE && c.obs_h == 84 && c.obs_w == 84 &&
-        c.fov_h == 30 && c.fov_w == 30 && ctx->k1.y_affine && ctx->band_rows == 12 && c.frame_stack >= 1) {
-        DeviceGuard g(c.device);
-        const IngestParams pi = ingest_params(ctx, d_frames, d_cmd);
-        FovParams pf = fov_params(ctx, d_action, action_dtype, nullptr, nullptr, d_obs, d_fov_loc, nullptr);
-        pf.cmd = d_cmd;
-        pf.phase = 3;                                        // `head` is the pre-ingest head, every slot is processed
-        pf.head = ctx->head[ctx->cur_head];
-        const size_t team_lds = (std::max(ingest_lds(ctx), fixed_lds(c)) + 15) & ~(size_t)15;
-        using GS = GeomS<84, 84, 30, 30>;
-        StepEnvArgs sa;
-        sa.pi = pi;
-        sa.pf = pf;
-        sa.team_lds = (int32_t)team_lds;
-        sa.debug = env_int("AGX_STEP_ENV_DEBUG", 0);
-        hipLaunchKernelGGL((k_step_env<GS>), dim3(c.num_envs), dim3(2 * kThreads), 2 * team_lds, S(stream), sa);
-        AGX_HIP(ctx, hipGetLastError());
-        ctx->cur_head ^= 1;
-        ctx->cur_fov ^= 1;
-        return AGX_OK;
-    }
-    if (parts > 1 && default_forms && c.obs_h == c.obs_w && !mid_event) {
-        DeviceGuard g(c.device);
-        if (!ctx->ev_fork) {
-            int lo_p = 0, hi_p = 0;
-            AGX_HIP(ctx, hipDeviceGetStreamPriorityRange(&lo_p, &hi_p));        // lo_p: least urgent (largest number)
-            const int prio = tn.aux_prio > 0 ? hi_p : (tn.aux_prio < 0 ? lo_p : 0);
-            for (int k = 0; k < 3; ++k) {
-                AGX_HIP(ctx, hipStreamCreateWithPriority(&ctx->aux[k], hipStreamNonBlocking, prio));
-                AGX_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_join[k], hipEventDisableTiming));
-            }
-            AGX_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_fork, hipEventDisableTiming));
-        }
-        hipStream_t st[4] = {S(stream), ctx->aux[0], ctx->aux[1], ctx->aux[2]};
-        AGX_HIP(ctx, hipEventRecord(ctx->ev_fork, st[0]));
-        for (int k = 1; k < parts; ++k) AGX_HIP(ctx, hipStreamWaitEvent(st[k], ctx->ev_fork, 0));
-        const size_t fsz = (size_t)c.obs_h * c.obs_w;
-        const bool crop = c.out_mode == AGX_OUT_RAW;
-        const size_t obs_env = (size_t)c.frame_stack * (crop ? (size_t)c.fov_h * c.fov_w : fsz);
-        const bool wide = action_dtype == AGX_DT_F64 || action_dtype == AGX_DT_I64;
-        const bool full12 = ctx->k1.y_affine && ctx->band_rows == 12 && c.obs_h % 12 == 0;
-        const bool headline = c.obs_h == 84 && c.obs_w == 84 && c.fov_h == 30 && c.fov_w == 30;
-        using GS = GeomS<84, 84, 30, 30>;
-        const GeomR gr{c.obs_h, c.obs_w, c.fov_h, c.fov_w};
-        int n0[5];
-        for (int k = 0; k <= parts; ++k) n0[k] = (int)((long long)c.num_envs * k / parts);
-        const IngestParams pi0 = ingest_params(ctx, d_frames, d_cmd);
-        for (int k = 0; k < parts; ++k) {
-            IngestParams q = pi0;
-            const size_t b = n0[k];
-            q.frames += b * 2 * (size_t)kRawFrameBytes;
-            q.cmd += b;
-            q.ring += b * c.frame_stack * fsz;
-            q.head_in += b;
-            q.head_out += b;
-            const dim3 grid(q.nbands, n0[k + 1] - n0[k]);
-            if (full12) hipLaunchKernelGGL(k_ingest_full12_part, grid, dim3(kThreads), ingest_lds(ctx), st[k], q);
-            else hipLaunchKernelGGL(k_ingest_part, grid, dim3(kThreads), ingest_lds(ctx), st[k], q);
-        }
-        AGX_HIP(ctx, hipGetLastError());
-        ctx->cur_head ^= 1;
-        const FovParams pf0 = fov_params(ctx, d_action, action_dtype, nullptr, nullptr, d_obs, d_fov_loc, nullptr);
-        for (int k = 0; k < parts; ++k) {
-            FovParams q = pf0;
-            const size_t b = n0[k];
-            q.ring += b * c.frame_stack * fsz;
-            q.head += b;
-            q.loc_in += 2 * b;
-            q.loc_out += 2 * b;
-            q.res_in += 2 * b;
-            q.res_out += 2 * b;
-            if (q.action) q.action = static_cast<const char *>(q.action) + b * (wide ? 16 : 8);
-            q.obs += b * obs_env;
-            if (q.user_loc) q.user_loc += 2 * b;
-            const dim3 grid(c.frame_stack, n0[k + 1] - n0[k]);
-            const size_t lds = fixed_lds(c);
-#define LAUNCH_PART(MODE)                                                                                              \
-    do {                                                                                                               \
-        if (headline) hipLaunchKernelGGL((k_fovea_fixed_part<GS, MODE>), grid, dim3(kThreads), lds, st[k], GS{}, q);   \
-        else hipLaunchKernelGGL((k_fovea_fixed_part<GeomR, MODE>), grid, dim3(kThreads), lds, st[k], gr, q);           \
-    } while (0)
-            switch (c.out_mode) {
-                case AGX_OUT_RAW: LAUNCH_PART(AGX_OUT_RAW); break;
-                case AGX_OUT_MASK: LAUNCH_PART(AGX_OUT_MASK); break;
-                default: LAUNCH_PART(AGX_OUT_RESIZE); break;
-            }
-#undef LAUNCH_PART
-        }
-        AGX_HIP(ctx, hipGetLastError());
-        ctx->cur_fov ^= 1;
-        for (int k = 1; k < parts; ++k) {
-            AGX_HIP(ctx, hipEventRecord(ctx->ev_join[k - 1], st[k]));
-            AGX_HIP(ctx, hipStreamWaitEvent(st[0], ctx->ev_join[k - 1], 0));
-        }
-        return AGX_OK;
-    }
-    if (!(c.out_mode != AGX_OUT_RESIZE || ctx->ingest_t != 256 || !fused || c.obs_h != c.obs_w)) {
-        DeviceGuard g(c.device);
-        const IngestParams pi = ingest_params(ctx, d_frames, d_cmd);
-        FovParams pf = fov_params(ctx, d_action, action_dtype, nullptr, nullptr, d_obs, d_fov_loc, nullptr);
-        pf.cmd = d_cmd;
-        pf.phase = 1;
-        pf.head = ctx->head[ctx->cur_head];                  // the head BEFORE this step's ingest
-        const bool b12 = ctx->tune.fused >= 2 && ctx->k1.band12_ok && ctx->band_rows == 12;      // AGX_STEP_FUSED=2 / 3: band12 ingest body
-        const size_t lds = std::max(b12 ? band12_lds(ctx) : ingest_lds(ctx), fixed_lds(c));
-        const dim3 grid1(pi.nbands + c.frame_stack, c.num_envs), grid2(1, c.num_envs), block(kThreads);
-        using GS = GeomS<84, 84, 30, 30>;
-        const GeomR gr{c.obs_h, c.obs_w, c.fov_h, c.fov_w};
-        if (b12 && headline && ctx->tune.fused == 3)
-            hipLaunchKernelGGL((k_step_fixed12_ff<GS>), grid1, block, lds, S(stream), GS{}, pi, pf);
-        else if (b12 && headline)
-            hipLaunchKernelGGL((k_step_fixed12<GS>), grid1, block, lds, S(stream), GS{}, pi, pf);
-        else if (headline)
-            hipLaunchKernelGGL((k_step_fixed<GS>), grid1, block, lds, S(stream), GS{}, pi, pf);
-        else
-            hipLaunchKernelGGL((k_step_fixed<GeomR>), grid1, block, lds, S(stream), gr, pi, pf);
-        AGX_HIP(ctx, hipGetLastError());
-        ctx->cur_head ^= 1;
-        if (mid_event) AGX_HIP(ctx, hipEventRecord(static_cast<hipEvent_t>(mid_event), S(stream)));
-        pf.phase = 2;
-        pf.head = ctx->head[ctx->cur_head];                  // the head AFTER the ingest
-        if (headline)
-            hipLaunchKernelGGL((k_step_fixed_tail<GS>), grid2, block, fixed_lds(c), S(stream), GS{}, pf);
-        else
-            hipLaunchKernelGGL((k_step_fixed_tail<GeomR>), grid2, block, fixed_lds(c), S(stream), gr, pf);
-        AGX_HIP(ctx, hipGetLastError());
-        ctx->cur_fov ^= 1;
-        return AGX_OK;
-    }
+    if (exp_step_fixed(ctx, d_frames, d_cmd, d_action, action_dtype, d_obs, d_fov_loc, mid_event, stream, &rc)) return rc;
 #endif
     rc = agx_ingest(ctx, d_frames, d_cmd, stream);
     if (rc) return rc;
@@ -1369,29 +1063,22 @@ int agx_fovea_peripheral(agx_ctx *ctx, const void *d_action, int action_dtype, c
     DeviceGuard g(c.device);
     FovParams p = fov_params(ctx, d_action, action_dtype, nullptr, d_mask, d_obs, d_fov_loc, nullptr);
     fov_range(ctx, p);
-    const int en = ctx->rng_n;             // envs of the launch
-    const GeomR gr{c.obs_h, c.obs_w, c.fov_h, c.fov_w};
-    const bool generic_only = ctx->tune.generic != 0;                               // tuning / testing knob
-    const int planes = c.frame_stack * ctx->planes;                                  // workgroups per env
+    const FovPlan &pl = ctx->plan;
+    const dim3 grid(c.frame_stack * ctx->planes, ctx->rng_n), block(kThreads);     // rng_n: the envs of the launch
     with_planes(ctx->planes, [&](auto pc) {
     constexpr int NC = decltype(pc)::value;
     return with_obs_type(ctx->obs_type, [&](auto tag) {
     using OT = decltype(tag);
-    if (!generic_only && ctx->p3_mt && ctx->tune.per_v2 == 0) {
-        const dim3 grid(planes, en), block(kThreads);
-        const size_t lds = ctx->p3_lds;
-        using GS = PGeomS<84, 84, 30, 30, 20, 20>;
+    if (pl.form == kFormPer3) {
         const PGeomR pg{c.obs_h, c.obs_w, c.fov_h, c.fov_w, c.per_h, c.per_w};
-        const bool headline = c.obs_h == 84 && c.obs_w == 84 && c.fov_h == 30 && c.fov_w == 30 && c.per_h == 20 && c.per_w == 20;
-        if (headline && ctx->p3_mt == 12) AGX_LAUNCH(1, (k_fovea_peripheral3<GS, 12, OT, NC>), grid, block, lds, S(stream), GS{}, ctx->p3, p);
-        else if (headline && ctx->p3_mt == 4) AGX_LAUNCH(1, (k_fovea_peripheral3<GS, 4, OT, NC>), grid, block, lds, S(stream), GS{}, ctx->p3, p);
-        else if (ctx->p3_mt == 4) AGX_LAUNCH(1, (k_fovea_peripheral3<PGeomR, 4, OT, NC>), grid, block, lds, S(stream), pg, ctx->p3, p);
-        else if (ctx->p3_mt == 8) AGX_LAUNCH(1, (k_fovea_peripheral3<PGeomR, 8, OT, NC>), grid, block, lds, S(stream), pg, ctx->p3, p);
-        else if (ctx->p3_mt == 12) AGX_LAUNCH(1, (k_fovea_peripheral3<PGeomR, 12, OT, NC>), grid, block, lds, S(stream), pg, ctx->p3, p);
-        else AGX_LAUNCH(1, (k_fovea_peripheral3<PGeomR, 16, OT, NC>), grid, block, lds, S(stream), pg, ctx->p3, p);
-    } else
-    // the tuned kernel keeps A | B | C with C 16-byte aligned and one row sweep per 256 threads
-    if (!generic_only && per2_lds(c) <= kMaxLds && c.per_w <= kThreads) {
+        using GS = PGeomS<84, 84, 30, 30, 20, 20>;
+        if (pl.headline && pl.mt == 12) AGX_LAUNCH(1, (k_fovea_peripheral3<GS, 12, OT, NC>), grid, block, pl.lds, S(stream), GS{}, ctx->p3, p);
+        else if (pl.headline) AGX_LAUNCH(1, (k_fovea_peripheral3<GS, 4, OT, NC>), grid, block, pl.lds, S(stream), GS{}, ctx->p3, p);
+        else if (pl.mt == 4) AGX_LAUNCH(1, (k_fovea_peripheral3<PGeomR, 4, OT, NC>), grid, block, pl.lds, S(stream), pg, ctx->p3, p);
+        else if (pl.mt == 8) AGX_LAUNCH(1, (k_fovea_peripheral3<PGeomR, 8, OT, NC>), grid, block, pl.lds, S(stream), pg, ctx->p3, p);
+        else if (pl.mt == 12) AGX_LAUNCH(1, (k_fovea_peripheral3<PGeomR, 12, OT, NC>), grid, block, pl.lds, S(stream), pg, ctx->p3, p);
+        else AGX_LAUNCH(1, (k_fovea_peripheral3<PGeomR, 16, OT, NC>), grid, block, pl.lds, S(stream), pg, ctx->p3, p);
+    } else if (pl.form == kFormPeripheral2) {
         PerParams g;
         for (int k = 0; k < 4; ++k) {
             g.t[k].ln = ctx->per_ln[k];
@@ -1400,21 +1087,17 @@ int agx_fovea_peripheral(agx_ctx *ctx, const void *d_action, int action_dtype, c
         }
         g.t[0].n_out = c.per_w; g.t[1].n_out = c.per_h; g.t[2].n_out = c.obs_w; g.t[3].n_out = c.obs_h;
         g.oh = c.obs_h; g.ow = c.obs_w; g.fh = c.fov_h; g.fw = c.fov_w; g.ph = c.per_h; g.pw = c.per_w;
-        g.same = (c.per_h == c.obs_h && c.per_w == c.obs_w) ? 1 : 0;                // torchvision returns the input
-        const int mt = std::max(ctx->per_maxt[0], ctx->per_maxt[1]);
-        const dim3 grid(planes, en), block(kThreads);
-        const size_t lds = per2_lds(c);
-        // both squeeze tables are padded to their own bucket; the kernel bound must not exceed either row pitch
-        const bool same_bucket = ctx->per_maxt[0] == ctx->per_maxt[1];
-        if (same_bucket && mt == 2) AGX_LAUNCH(1, (k_fovea_peripheral2<2, OT, NC>), grid, block, lds, S(stream), g, p);
-        else if (same_bucket && mt == 4) AGX_LAUNCH(1, (k_fovea_peripheral2<4, OT, NC>), grid, block, lds, S(stream), g, p);
-        else if (same_bucket && mt == 8) AGX_LAUNCH(1, (k_fovea_peripheral2<8, OT, NC>), grid, block, lds, S(stream), g, p);
-        else if (same_bucket && mt == 12) AGX_LAUNCH(1, (k_fovea_peripheral2<12, OT, NC>), grid, block, lds, S(stream), g, p);
-        else if (same_bucket && mt == 16) AGX_LAUNCH(1, (k_fovea_peripheral2<16, OT, NC>), grid, block, lds, S(stream), g, p);
-        else AGX_LAUNCH(1, (k_fovea_peripheral2<0, OT, NC>), grid, block, lds, S(stream), g, p);
+        g.same = pl.same;
+        switch (pl.mt) {
+            case 2: AGX_LAUNCH(1, (k_fovea_peripheral2<2, OT, NC>), grid, block, pl.lds, S(stream), g, p); break;
+            case 4: AGX_LAUNCH(1, (k_fovea_peripheral2<4, OT, NC>), grid, block, pl.lds, S(stream), g, p); break;
+            case 8: AGX_LAUNCH(1, (k_fovea_peripheral2<8, OT, NC>), grid, block, pl.lds, S(stream), g, p); break;
+            case 12: AGX_LAUNCH(1, (k_fovea_peripheral2<12, OT, NC>), grid, block, pl.lds, S(stream), g, p); break;
+            case 16: AGX_LAUNCH(1, (k_fovea_peripheral2<16, OT, NC>), grid, block, pl.lds, S(stream), g, p); break;
+            default: AGX_LAUNCH(1, (k_fovea_peripheral2<0, OT, NC>), grid, block, pl.lds, S(stream), g, p); break;
+        }
     } else {
-        hipLaunchKernelGGL((k_fovea_generic<AGX_KIND_PERIPHERAL, OT, NC>), dim3(planes, en), dim3(kThreads),
-                           generic_lds(c), S(stream), gr, p);
+        hipLaunchKernelGGL((k_fovea_generic<AGX_KIND_PERIPHERAL, OT, NC>), grid, block, pl.lds, S(stream), geom_r(c), p);
     }
     return 0;
     });
@@ -1436,48 +1119,30 @@ int agx_fovea_flexible(agx_ctx *ctx, const void *d_action, int action_dtype, con
     DeviceGuard g(c.device);
     FovParams p = fov_params(ctx, d_action, action_dtype, d_action_type, d_mask, d_obs, d_fov_loc, d_fov_res);
     fov_range(ctx, p);
-    const int en = ctx->rng_n;             // envs of the launch
-    const GeomR gr{c.obs_h, c.obs_w, c.fov_h, c.fov_w};
-    const bool generic_only = ctx->tune.generic != 0;                               // tuning / testing knob
-    const size_t lds2 = flex2_lds(c, ctx->flex_tab_floats);
-    const int planes = c.frame_stack * ctx->planes;                                  // workgroups per env
+    const FovPlan &pl = ctx->plan;
+    const dim3 grid(c.frame_stack * ctx->planes, ctx->rng_n), block(kThreads);     // rng_n: the envs of the launch
     with_planes(ctx->planes, [&](auto pc) {
     constexpr int NC = decltype(pc)::value;
     return with_obs_type(ctx->obs_type, [&](auto tag) {
     using OT = decltype(tag);
-    if (!generic_only && ctx->f3_ok && ctx->tune.flex_v2 == 0) {
-        const size_t lds3 = (size_t)ctx->f3.r0_bytes + ctx->f3.r1_bytes + (size_t)c.obs_h * sizeof(int4);
-        const dim3 grid(planes, en), block(kThreads);
-        using GS = GeomS<84, 84, 30, 30>;
-        if (c.obs_h == 84 && c.obs_w == 84 && c.fov_h == 30 && c.fov_w == 30)
-            AGX_LAUNCH(1, (k_fovea_flexible3<GS, OT, NC>), grid, block, lds3, S(stream), GS{}, ctx->f3, p);
-        else
-            AGX_LAUNCH(1, (k_fovea_flexible3<GeomR, OT, NC>), grid, block, lds3, S(stream), gr, ctx->f3, p);
-    } else if (!generic_only && ctx->fr_ok && ctx->tune.flex_v2 == 0 && c.out_mode != AGX_OUT_RESIZE) {
-        const dim3 grid(planes, en), block(kThreads);
-        using GS = GeomS<84, 84, 30, 30>;
-        const bool headline = c.obs_h == 84 && c.obs_w == 84 && c.fov_h == 30 && c.fov_w == 30;
-        if (c.out_mode == AGX_OUT_MASK) {
-            if (headline) AGX_LAUNCH(1, (k_fovea_flexible_raw3<GS, AGX_OUT_MASK, OT, NC>), grid, block, ctx->fr_lds, S(stream), GS{}, ctx->fr, p);
-            else AGX_LAUNCH(1, (k_fovea_flexible_raw3<GeomR, AGX_OUT_MASK, OT, NC>), grid, block, ctx->fr_lds, S(stream), gr, ctx->fr, p);
-        } else {
-            if (headline) AGX_LAUNCH(1, (k_fovea_flexible_raw3<GS, AGX_OUT_RAW, OT, NC>), grid, block, ctx->fr_lds, S(stream), GS{}, ctx->fr, p);
-            else AGX_LAUNCH(1, (k_fovea_flexible_raw3<GeomR, AGX_OUT_RAW, OT, NC>), grid, block, ctx->fr_lds, S(stream), gr, ctx->fr, p);
-        }
-    } else if (!generic_only && lds2 <= kMaxLds) {
-        FlexParams g;
-        TabFamily *fam[6] = {&g.wd, &g.wb, &g.wf, &g.hd, &g.hb, &g.hf};
-        for (int k = 0; k < 6; ++k) {
-            fam[k]->ln = ctx->flex_ln[k];
-            fam[k]->w = ctx->flex_w[k];
-            fam[k]->meta = ctx->flex_meta[k];
-        }
-        g.oh = c.obs_h; g.ow = c.obs_w; g.fh = c.fov_h; g.fw = c.fov_w;
-        if (c.out_mode == AGX_OUT_RESIZE) AGX_LAUNCH(1, (k_fovea_flexible2<true, OT, NC>), dim3(planes, en), dim3(kThreads), lds2, S(stream), g, p);
-        else AGX_LAUNCH(1, (k_fovea_flexible2<false, OT, NC>), dim3(planes, en), dim3(kThreads), lds2, S(stream), g, p);
+    if (pl.form == kFormFlex3) {
+        return with_geom(pl.headline, geom_r(c), [&](auto g) {
+            AGX_LAUNCH(1, (k_fovea_flexible3<decltype(g), OT, NC>), grid, block, pl.lds, S(stream), g, ctx->f3, p);
+            return 0;
+        });
+    } else if (pl.form == kFormRaw3) {
+        return with_geom(pl.headline, geom_r(c), [&](auto g) {
+            using G = decltype(g);
+            if (c.out_mode == AGX_OUT_MASK) AGX_LAUNCH(1, (k_fovea_flexible_raw3<G, AGX_OUT_MASK, OT, NC>), grid, block, pl.lds, S(stream), g, ctx->fr, p);
+            else AGX_LAUNCH(1, (k_fovea_flexible_raw3<G, AGX_OUT_RAW, OT, NC>), grid, block, pl.lds, S(stream), g, ctx->fr, p);
+            return 0;
+        });
+    } else if (pl.form == kFormFlexible2) {
+        const FlexParams g = flex_params(ctx);
+        if (c.out_mode == AGX_OUT_RESIZE) AGX_LAUNCH(1, (k_fovea_flexible2<true, OT, NC>), grid, block, pl.lds, S(stream), g, p);
+        else AGX_LAUNCH(1, (k_fovea_flexible2<false, OT, NC>), grid, block, pl.lds, S(stream), g, p);
     } else {
-        hipLaunchKernelGGL((k_fovea_generic<AGX_KIND_FLEXIBLE, OT, NC>), dim3(planes, en), dim3(kThreads),
-                           generic_lds(c), S(stream), gr, p);
+        hipLaunchKernelGGL((k_fovea_generic<AGX_KIND_FLEXIBLE, OT, NC>), grid, block, pl.lds, S(stream), geom_r(c), p);
     }
     return 0;
     });
@@ -1488,48 +1153,44 @@ int agx_fovea_flexible(agx_ctx *ctx, const void *d_action, int action_dtype, con
     return AGX_OK;
 }
 
-// the state / scan launch of the packed form (fov_env.py:300-324 + level 1 of the exclusive scan of the crop sizes; the scratch
-// belongs to the context since agx_create)
-static FlexScanParams packed_scan_params(agx_ctx *ctx, const void *d_action, int action_dtype, const int32_t *d_action_type,
-                                         int32_t *d_fov_loc, int32_t *d_fov_res) {
-    FlexScanParams q;
-    q.f = fov_params(ctx, d_action, action_dtype, d_action_type, nullptr, nullptr, d_fov_loc, d_fov_res);
-    q.local_off = ctx->pack_local;
-    q.block_tot = ctx->pack_block;
-    q.n = ctx->cfg.num_envs;
-    q.oh = ctx->cfg.obs_h;
-    q.ow = ctx->cfg.obs_w;
-    return q;
-}
-static bool packed_raw3_ok(const agx_ctx *ctx) { return ctx->fr_ok && ctx->tune.generic == 0 && ctx->tune.flex_v2 == 0; }
-
-// the crop launch of the packed form on the raw3 plan (the state is final: cur_fov has been flipped by the caller)
-static int packed_crops_raw3(agx_ctx *ctx, float *d_packed, int64_t capacity_floats, int64_t *d_offsets, void *stream) {
-    const agx_config &c = ctx->cfg;
+// the crop launches of the packed form read the final state (cur_fov has been flipped by the caller) and write ragged crops
+static FovParams packed_fov_params(agx_ctx *ctx, float *d_packed, int64_t capacity_floats, int64_t *d_offsets) {
     FovParams p = fov_params(ctx, nullptr, 0, nullptr, nullptr, d_packed, nullptr, nullptr);
     p.packed = d_packed;
     p.packed_off = d_offsets;
     p.packed_cap = capacity_floats;
-    const GeomR gr{c.obs_h, c.obs_w, c.fov_h, c.fov_w};
+    return p;
+}
+
+// the crop launch of the packed form on the raw3 plan
+static int packed_crops_raw3(agx_ctx *ctx, float *d_packed, int64_t capacity_floats, int64_t *d_offsets, void *stream) {
+    const agx_config &c = ctx->cfg;
+    const FovParams p = packed_fov_params(ctx, d_packed, capacity_floats, d_offsets);
     FlexRawParams fr = ctx->fr;
     fr.local_off = ctx->pack_local;
     fr.block_tot = ctx->pack_block;
     fr.offsets = d_offsets;
     const dim3 grid(c.frame_stack, c.num_envs), block(kThreads);
-    using GS = GeomS<84, 84, 30, 30>;
 #ifdef AGX_EXPERIMENTS
-    if (ctx->tune.packed_wave != 0) {              // one wave per (slot, env) item: measured slower (docs/HISTORY.md, round 4)
-        if (c.obs_h == 84 && c.obs_w == 84 && c.fov_h == 30 && c.fov_w == 30)
-            AGX_LAUNCH(1, (k_fovea_flexible_raw3_wave<GS>), grid, dim3(64), ctx->fr_lds, S(stream), GS{}, fr, p);
-        else
-            AGX_LAUNCH(1, (k_fovea_flexible_raw3_wave<GeomR>), grid, dim3(64), ctx->fr_lds, S(stream), gr, fr, p);
-    } else
+    if (!exp_packed_crops_raw3(ctx, fr, p, stream))
 #endif
-    if (c.obs_h == 84 && c.obs_w == 84 && c.fov_h == 30 && c.fov_w == 30)
-        AGX_LAUNCH(1, (k_fovea_flexible_raw3<GS, kRawPacked>), grid, block, ctx->fr_lds, S(stream), GS{}, fr, p);
-    else
-        AGX_LAUNCH(1, (k_fovea_flexible_raw3<GeomR, kRawPacked>), grid, block, ctx->fr_lds, S(stream), gr, fr, p);
+        with_geom(ctx->plan.headline, geom_r(c), [&](auto g) {
+            AGX_LAUNCH(1, (k_fovea_flexible_raw3<decltype(g), kRawPacked>), grid, block, ctx->plan.lds, S(stream), g, fr, p);
+            return 0;
+        });
     AGX_HIP(ctx, hipGetLastError());
+    return AGX_OK;
+}
+
+// what both packed entry points require of the context
+static int packed_check(agx_ctx *ctx, const char *who) {
+    const agx_config &c = ctx->cfg;
+    if (ctx->planes != 1) return refuse_rgb(ctx, who);
+    if (!full_range(ctx)) return refuse_range(ctx, who);
+    if (c.kind != AGX_KIND_FLEXIBLE || c.out_mode != AGX_OUT_RAW)
+        return fail(ctx, AGX_E_STATE, "%s needs a flexible context in raw-crop mode (kind %d, out_mode %d)", who, c.kind, c.out_mode);
+    if (ctx->obs_type != AGX_OBS_F32)
+        return fail(ctx, AGX_E_STATE, "%s: the packed ragged crops are float32 only (context has AGX_OBS_* 0x%x)", who, ctx->obs_type);
     return AGX_OK;
 }
 
@@ -1538,17 +1199,10 @@ int agx_fovea_flexible_packed(agx_ctx *ctx, const void *d_action, int action_dty
                               int32_t *d_fov_res, void *stream) {
     if (!ctx) return AGX_E_INVALID;
     const agx_config &c = ctx->cfg;
-    if (ctx->planes != 1) return refuse_rgb(ctx, "agx_fovea_flexible_packed");
-    if (!full_range(ctx)) return refuse_range(ctx, "agx_fovea_flexible_packed");
-    if (c.kind != AGX_KIND_FLEXIBLE || c.out_mode != AGX_OUT_RAW)
-        return fail(ctx, AGX_E_STATE, "agx_fovea_flexible_packed needs a flexible context in raw-crop mode (kind %d, out_mode %d)",
-                    c.kind, c.out_mode);
-    if (ctx->obs_type != AGX_OBS_F32)
-        return fail(ctx, AGX_E_STATE, "agx_fovea_flexible_packed: the packed ragged crops are float32 only (context has AGX_OBS_* 0x%x)",
-                    ctx->obs_type);
-    if (!d_packed || !d_offsets || capacity_floats < 0) return fail(ctx, AGX_E_INVALID, "agx_fovea_flexible_packed: null buffer");
-    int rc = check_dt(ctx, d_action, action_dtype);
+    int rc = packed_check(ctx, "agx_fovea_flexible_packed");
     if (rc) return rc;
+    if (!d_packed || !d_offsets || capacity_floats < 0) return fail(ctx, AGX_E_INVALID, "agx_fovea_flexible_packed: null buffer");
+    if ((rc = check_dt(ctx, d_action, action_dtype))) return rc;
     DeviceGuard g(c.device);
     // launch 1: every env's new fov_loc / fov_res (fov_env.py:300-324), its crop size, and level 1 of the exclusive scan
     // (block-local offsets + block totals)
@@ -1558,31 +1212,17 @@ int agx_fovea_flexible_packed(agx_ctx *ctx, const void *d_action, int action_dty
     AGX_HIP(ctx, hipGetLastError());
     ctx->cur_fov ^= 1;                   // the state is final from here on; the crop launch only reads it
     // launch 2: the crops (squeezed to fov_size and back iff rows > fov rows, fov_env.py:283-287) at their offsets
-    if (packed_raw3_ok(ctx)) return packed_crops_raw3(ctx, d_packed, capacity_floats, d_offsets, stream);
-    FovParams p = fov_params(ctx, nullptr, 0, nullptr, nullptr, d_packed, nullptr, nullptr);
-    p.packed = d_packed;
-    p.packed_off = d_offsets;
-    p.packed_cap = capacity_floats;
-    const GeomR gr{c.obs_h, c.obs_w, c.fov_h, c.fov_w};
+    if (ctx->plan.packed == kPackedRaw3) return packed_crops_raw3(ctx, d_packed, capacity_floats, d_offsets, stream);
+    const FovParams p = packed_fov_params(ctx, d_packed, capacity_floats, d_offsets);
     // geometries outside the raw3 plan: offsets as a launch of their own, then the pass-by-pass crop kernel, which writes
     // the (unchanged) state through into the other half of the double buffer
     hipLaunchKernelGGL(k_flex_finish_offsets, dim3((c.num_envs + 1 + kThreads - 1) / kThreads), dim3(kThreads), 0, S(stream),
                        ctx->pack_local, ctx->pack_block, d_offsets, (int)c.num_envs);
-    const size_t lds2 = flex2_lds(c, ctx->flex_tab_floats);
-    if (ctx->tune.generic == 0 && lds2 <= kMaxLds) {
-        FlexParams fp;
-        TabFamily *fam[6] = {&fp.wd, &fp.wb, &fp.wf, &fp.hd, &fp.hb, &fp.hf};
-        for (int k = 0; k < 6; ++k) {
-            fam[k]->ln = ctx->flex_ln[k];
-            fam[k]->w = ctx->flex_w[k];
-            fam[k]->meta = ctx->flex_meta[k];
-        }
-        fp.oh = c.obs_h; fp.ow = c.obs_w; fp.fh = c.fov_h; fp.fw = c.fov_w;
-        AGX_LAUNCH(1, k_fovea_flexible2<false>, dim3(c.frame_stack, c.num_envs), dim3(kThreads), lds2, S(stream), fp, p);
-    } else {
-        hipLaunchKernelGGL((k_fovea_generic<AGX_KIND_FLEXIBLE>), dim3(c.frame_stack, c.num_envs), dim3(kThreads),
-                           generic_lds(c), S(stream), gr, p);
-    }
+    const dim3 grid(c.frame_stack, c.num_envs), block(kThreads);
+    if (ctx->plan.packed == kPackedOffsetsFlexible2)
+        AGX_LAUNCH(1, k_fovea_flexible2<false>, grid, block, ctx->plan.lds, S(stream), flex_params(ctx), p);
+    else
+        hipLaunchKernelGGL((k_fovea_generic<AGX_KIND_FLEXIBLE>), grid, block, ctx->plan.lds, S(stream), geom_r(c), p);
     AGX_HIP(ctx, hipGetLastError());
     ctx->cur_fov ^= 1;
     return AGX_OK;
@@ -1593,26 +1233,20 @@ int agx_step_flexible_packed(agx_ctx *ctx, const uint8_t *d_screens, int screens
                              int64_t *d_offsets, int32_t *d_fov_loc, int32_t *d_fov_res, void *stream) {
     if (!ctx) return AGX_E_INVALID;
     const agx_config &c = ctx->cfg;
-    if (ctx->planes != 1) return refuse_rgb(ctx, "agx_step_flexible_packed");
-    if (!full_range(ctx)) return refuse_range(ctx, "agx_step_flexible_packed");
-    if (c.kind != AGX_KIND_FLEXIBLE || c.out_mode != AGX_OUT_RAW)
-        return fail(ctx, AGX_E_STATE, "agx_step_flexible_packed needs a flexible context in raw-crop mode (kind %d, out_mode %d)",
-                    c.kind, c.out_mode);
-    if (ctx->obs_type != AGX_OBS_F32)
-        return fail(ctx, AGX_E_STATE, "agx_step_flexible_packed: the packed ragged crops are float32 only (context has AGX_OBS_* 0x%x)",
-                    ctx->obs_type);
+    int rc = packed_check(ctx, "agx_step_flexible_packed");
+    if (rc) return rc;
     if (!d_screens || !d_cmd || !d_packed || !d_offsets || capacity_floats < 0)
         return fail(ctx, AGX_E_INVALID, "agx_step_flexible_packed: null buffer");
     if (screens & ~(AGX_SCREENS_GRAY | AGX_SCREENS_COMPACT))
         return fail(ctx, AGX_E_INVALID, "agx_step_flexible_packed: unknown screen layout bits 0x%x", screens);
-    int rc = check_dt(ctx, d_action, action_dtype);
-    if (rc) return rc;
+    if ((rc = check_dt(ctx, d_action, action_dtype))) return rc;
     const bool gray = (screens & AGX_SCREENS_GRAY) != 0, compact = (screens & AGX_SCREENS_COMPACT) != 0;
     // the two-launch form needs the band12 ingest plan for this layout and the raw3 crop plan; everything else (and
     // AGX_STEP_PACKED_UNFUSED=1, for A/B runs) is the three launches of the stand-alone entry points, same results
-    const bool band12 = k1_band12(ctx->k1, compact, compact ? ctx->k1.band_rows : (gray ? gray_band_rows(ctx) : ctx->band_rows));
+    const int layout = (compact ? kK1RgbCompact : kK1Rgb) + (gray ? 1 : 0);
+    const K1Launch &l = ctx->k1l[layout];
     const int nb = (c.num_envs + kScanEnvsPerBlock - 1) / kScanEnvsPerBlock;
-    const bool fused = c.obs_h == c.obs_w && band12 && ctx->tune.no_full == 0 && packed_raw3_ok(ctx) && c.num_envs + nb <= 65535 &&
+    const bool fused = c.obs_h == c.obs_w && l.band12 && ctx->plan.packed == kPackedRaw3 && c.num_envs + nb <= 65535 &&
                        ctx->tune.packed_unfused == 0 && ctx->tune.packed_wave == 0 &&
                        ctx->tune.pipe_parts == 0 && ctx->tune.wave == 0 && ctx->tune.pair12 == 0 && ctx->ingest_t == 256;
     if (!fused) {
@@ -1623,18 +1257,11 @@ int agx_step_flexible_packed(agx_ctx *ctx, const uint8_t *d_screens, int screens
                                          d_fov_res, stream);
     }
     DeviceGuard g(c.device);
-    IngestParams p = ingest_params(ctx, d_screens, d_cmd);
-    p.band_rows = 12;
-    p.nbands = c.obs_h / 12;
-    if (compact) {
-        p.src_rows = (int32_t)ctx->src_rows.size();
-        p.ytab = ctx->in_ytab_c;
-        p.y_affine = 0;
-    }
+    const IngestParams p = ingest_params(ctx, d_screens, d_cmd, layout);
     const FlexScanParams q = packed_scan_params(ctx, d_action, action_dtype, d_action_type, d_fov_loc, d_fov_res);
     // launch 1: the scan blocks (first rows of the grid) + the ingest bands
-    const dim3 grid(p.nbands, nb + c.num_envs), block(kThreads);
-    const size_t lds = band12_lds(ctx);
+    const dim3 grid(l.nbands, nb + c.num_envs), block(kThreads);
+    const size_t lds = l.lds;
     if (compact) {
         if (gray) AGX_LAUNCH(0, (k_ingest_full12_flexscan<true, true>), grid, block, lds, S(stream), p, q, nb);
         else AGX_LAUNCH(0, (k_ingest_full12_flexscan<false, true>), grid, block, lds, S(stream), p, q, nb);

@@ -16,6 +16,12 @@ constexpr int kRawW = 160;
 constexpr int kRawRowBytes = kRawW * 3;
 constexpr int kRawFrameBytes = kRawH * kRawRowBytes;
 constexpr int kThreads = 256;
+// the band12 ingest form's LDS image (agx_k1_ingest.h: ingest_band12; agx_plan.h: band12_lds)
+constexpr int kB12Rows = 12;
+constexpr uint32_t kB12RowB = kRawW * 2;                                  // one u16 gray row
+constexpr uint32_t kB12JobB = 2 * kB12RowB;                               // top + bottom source row of one output row
+constexpr uint32_t kB12FrameB = kB12Rows * kB12JobB;
+constexpr uint32_t kB12GrayB = 2 * kB12FrameB;                            // 15,360 B
 
 // ---------------------------------------------------------------------------------------------
 // geometry: compile-time for the headline 84x84 / 30x30 configuration, run-time otherwise

@@ -4,13 +4,15 @@
 // bytes, so what K5 / K6 write is bit for bit what K2 wrote.
 #pragma once
 #include "agx_common.h"
+#include "agx_glimpse.h"
 #include "agx_obs_store.h"
 
 namespace agx {
 
 // ---- LDS carve: `windows` window images u8 [fh][ow] (16-B padded each) | ytab[oh] | H[fh][ow] (and whatever the caller keeps
-// behind it).  fixed_pad is the one expression of the padded window bytes (agx_api.hip: fixed_lds; agx_glimpse_impl.h: memory_lds).
+// behind it).  fixed_pad is the one expression of the padded window bytes (agx_plan.h: fixed_lds, memory_lds).
 __host__ __device__ constexpr int fixed_pad(int fh, int ow) { return (fh * ow + 15) & ~15; }
+constexpr int kMemTableBytes = AGX_GLIMPSE_LIMIT * 16;   // K6: the glimpse table int2[AGX_GLIMPSE_LIMIT] in front of the carve
 struct FixedCarve {
     unsigned char *raw;
     Tap *ytab_s;

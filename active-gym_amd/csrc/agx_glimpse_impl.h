@@ -3,20 +3,6 @@
 #pragma once
 #include "agx_glimpse.h"
 
-namespace {
-
-// the LDS carve of k_history_memory
-size_t memory_lds(const agx_config &c, int glimpses, bool headline) {
-    size_t b = agx::kMemTableBytes + (size_t)glimpses * agx::fixed_pad(c.fov_h, c.obs_w);
-    if (c.out_mode == AGX_OUT_RESIZE) {
-        b += (size_t)c.obs_h * sizeof(Tap) + 2 * (size_t)c.fov_h * c.obs_w * sizeof(float);
-        if (!headline) b += (size_t)c.obs_h * c.obs_w * sizeof(float);      // the running maximum of the run-time geometry form
-    }
-    return b;
-}
-
-}  // namespace
-
 extern "C" {
 
 int agx_history_observe_memory(agx_history *h, int32_t glimpses, const int32_t *d_env, const int64_t *d_index, int32_t B, float *d_obs,
@@ -32,7 +18,7 @@ int agx_history_observe_memory(agx_history *h, int32_t glimpses, const int32_t *
     if (c.out_mode == AGX_OUT_RAW)
         return fail(ctx, AGX_E_STATE, "agx_history_observe_memory: raw-crop mode is not served (a maximum over crops at different positions means nothing; mask-out and resize_to_full are)");
     if (!full_range(ctx)) return hist_refuse_range(h, "agx_history_observe_memory");
-    const bool headline = headline_fixed(c);
+    const bool headline = ctx->plan.headline;
     const size_t lds = memory_lds(c, glimpses, headline);
     if (lds > kMaxLds)
         return fail(ctx, AGX_E_STATE, "agx_history_observe_memory: %d glimpses of this geometry need %zu B of LDS per workgroup (limit %zu)", glimpses, lds,
@@ -48,9 +34,7 @@ int agx_history_observe_memory(agx_history *h, int32_t glimpses, const int32_t *
     agx::HistMemParams q;
     q.h = h->p;
     q.glimpses = glimpses;
-    using GS = GeomS<84, 84, 30, 30>;
-    const GeomR gr{c.obs_h, c.obs_w, c.fov_h, c.fov_w};
-    const size_t row_bytes = (size_t)c.frame_stack * (size_t)c.obs_h * c.obs_w * obs_elem_bytes(ctx->obs_type);
+    const size_t row_bytes = obs_row_bytes(ctx, false);
     // the sample index rides on gridDim.y: launches of at most 65535 samples
     for (int32_t at = 0; at < B; at += 65535) {
         const int nb = std::min<int32_t>(B - at, 65535);
@@ -61,22 +45,17 @@ int agx_history_observe_memory(agx_history *h, int32_t glimpses, const int32_t *
         q.loc_out = d_fov_loc ? d_fov_loc + 2 * (size_t)at * glimpses : nullptr;
         q.taken = d_taken ? d_taken + at : nullptr;
         const dim3 grid(c.frame_stack, nb), block(kThreads);
-#define LAUNCH(MODE)                                                                                             \
-    do {                                                                                                         \
-        if (headline)                                                                                            \
-            hipLaunchKernelGGL((agx::k_history_memory<GS, MODE, OT>), grid, block, lds, S(stream), GS{}, pp, q); \
-        else                                                                                                     \
-            hipLaunchKernelGGL((agx::k_history_memory<GeomR, MODE, OT>), grid, block, lds, S(stream), gr, pp, q); \
-    } while (0)
         with_obs_type(ctx->obs_type, [&](auto tag) {
-            using OT = decltype(tag);
-            if (c.out_mode == AGX_OUT_MASK)
-                LAUNCH(AGX_OUT_MASK);
-            else
-                LAUNCH(AGX_OUT_RESIZE);
-            return 0;
+            return with_geom(headline, geom_r(c), [&](auto g) {
+                using G = decltype(g);
+                using OT = decltype(tag);
+                if (c.out_mode == AGX_OUT_MASK)
+                    hipLaunchKernelGGL((agx::k_history_memory<G, AGX_OUT_MASK, OT>), grid, block, lds, S(stream), g, pp, q);
+                else
+                    hipLaunchKernelGGL((agx::k_history_memory<G, AGX_OUT_RESIZE, OT>), grid, block, lds, S(stream), g, pp, q);
+                return 0;
+            });
         });
-#undef LAUNCH
     }
     AGX_HIP(ctx, hipGetLastError());
     return AGX_OK;

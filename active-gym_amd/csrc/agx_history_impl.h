@@ -145,43 +145,29 @@ int agx_history_observe(agx_history *h, int what, const int32_t *d_env, const in
     agx::HistObsParams q;
     q.h = h->p;
     q.has_loc = fixed ? 1 : 0;
-    const int mode = what == AGX_HIST_FULL ? agx::kHistFull : c.out_mode;
-    const size_t lds = what == AGX_HIST_FULL ? 0 : fixed_lds(c);
-    const bool headline = headline_fixed(c);
-    using GS = GeomS<84, 84, 30, 30>;
-    const GeomR gr{c.obs_h, c.obs_w, c.fov_h, c.fov_w};
-    const bool crop = what == AGX_HIST_FOVEA && c.out_mode == AGX_OUT_RAW;
-    const size_t row_bytes = (size_t)c.frame_stack * (crop ? (size_t)c.fov_h * c.fov_w : (size_t)c.obs_h * c.obs_w) * obs_elem_bytes(ctx->obs_type);
-    const bool wide = action_dtype == AGX_DT_F64 || action_dtype == AGX_DT_I64;
+    const bool fovea = what == AGX_HIST_FOVEA;
+    const size_t lds = fovea ? ctx->plan.lds : 0;
+    const size_t row_bytes = obs_row_bytes(ctx, fovea && c.out_mode == AGX_OUT_RAW);
     // the sample index rides on gridDim.y: launches of at most 65535 samples
     for (int32_t at = 0; at < B; at += 65535) {
         const int nb = std::min<int32_t>(B - at, 65535);
         FovParams pp = p;
         pp.obs = reinterpret_cast<float *>(reinterpret_cast<char *>(d_obs) + (size_t)at * row_bytes);
-        if (pp.action) pp.action = static_cast<const char *>(pp.action) + (size_t)at * (wide ? 16 : 8);
+        if (pp.action) pp.action = static_cast<const char *>(pp.action) + (size_t)at * action_stride(action_dtype);
         if (pp.user_loc) pp.user_loc += 2 * (size_t)at;
         q.env = d_env + at;
         q.index = d_index + at;
         q.valid = d_valid ? d_valid + at : nullptr;
         const dim3 grid(c.frame_stack, nb), block(kThreads);
-#define LAUNCH(MODE)                                                                                              \
-    do {                                                                                                          \
-        if (headline)                                                                                             \
-            hipLaunchKernelGGL((agx::k_history_observe<GS, MODE, OT>), grid, block, lds, S(stream), GS{}, pp, q); \
-        else                                                                                                      \
-            hipLaunchKernelGGL((agx::k_history_observe<GeomR, MODE, OT>), grid, block, lds, S(stream), gr, pp, q); \
-    } while (0)
         with_obs_type(ctx->obs_type, [&](auto tag) {
-            using OT = decltype(tag);
-            switch (mode) {
-                case AGX_OUT_RAW: LAUNCH(AGX_OUT_RAW); break;
-                case AGX_OUT_MASK: LAUNCH(AGX_OUT_MASK); break;
-                case AGX_OUT_RESIZE: LAUNCH(AGX_OUT_RESIZE); break;
-                default: LAUNCH(agx::kHistFull); break;
-            }
-            return 0;
+            return with_geom(ctx->plan.headline, geom_r(c), [&](auto g) {
+                auto launch = [&](auto mode) {
+                    hipLaunchKernelGGL((agx::k_history_observe<decltype(g), decltype(mode)::value, decltype(tag)>), grid, block, lds, S(stream), g, pp, q);
+                    return 0;
+                };
+                return fovea ? with_mode(c.out_mode, launch) : launch(std::integral_constant<int, agx::kHistFull>{});
+            });
         });
-#undef LAUNCH
     }
     AGX_HIP(ctx, hipGetLastError());
     return AGX_OK;

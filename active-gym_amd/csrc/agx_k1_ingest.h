@@ -382,12 +382,7 @@ __device__ __forceinline__ uint32_t ale_lum_tie(uint32_t r, uint32_t g, uint32_t
 }
 struct __attribute__((packed, aligned(4))) U2a4 { uint32_t x, y; };      // two dwords at a 4-byte-aligned LDS address
 
-constexpr int kB12Rows = 12;
-constexpr uint32_t kB12RowB = kRawW * 2;                                  // one u16 gray row
-constexpr uint32_t kB12JobB = 2 * kB12RowB;                               // top + bottom source row of one output row
-constexpr uint32_t kB12FrameB = kB12Rows * kB12JobB;
-constexpr uint32_t kB12GrayB = 2 * kB12FrameB;                            // 15,360 B
-
+// (kB12Rows .. kB12GrayB, the byte counts of this form's LDS image: agx_common.h, where the host plan reads them too)
 // LDS: ytab12[12] int2 | xtab12[ow] int2 | gray16 [2][12][2][160] u16
 // COMPACT: packed source rows (see IngestParams::src_rows): output row dy reads packed rows 2 dy and 2 dy + 1 - no row
 // arithmetic at all, and every byte of every 128-B line the kernel touches is used.

@@ -39,9 +39,9 @@ struct MemPasses<GeomS<OH, OW, FH, FW>> {
 //   RESIZE:  per glimpse phase C (H, double-buffered: one barrier per glimpse) and phase D with the running maximum;
 //            one pass of store_obs at the end.  The first glimpse assigns, so P = 1 is k_history_observe bit for bit.
 // LDS carve: glimpse table int2[AGX_GLIMPSE_LIMIT] (r, c) | P windows u8 [fh][ow] (16-B padded each) | ytab[oh] | H[2][fh][ow]
-//            (fixed_carve with P windows) | acc[oh][ow] (run-time geometry only)            (agx_glimpse_impl.h: memory_lds)
+//            (fixed_carve with P windows) | acc[oh][ow] (run-time geometry only)            (agx_plan.h: memory_lds)
 // ---------------------------------------------------------------------------------------------
-constexpr int kMemTableBytes = AGX_GLIMPSE_LIMIT * 16;
+// (kMemTableBytes, the glimpse table's bytes: agx_fixed_phases.h, beside fixed_pad)
 
 template <class G, int MODE, class OT>
 __global__ __launch_bounds__(kThreads) void k_history_memory(G g, FovParams p, HistMemParams q) {

@@ -1,4 +1,5 @@
-// CPU harness for the host-built operator tables of k_fovea_flexible3 (active-gym_amd/csrc/agx_host_tables.h).
+// CPU harness for the host-built operator tables of k_fovea_flexible3 (active-gym_amd/csrc/agx_host_tables.h) and the
+// host plan (active-gym_amd/csrc/agx_plan.h).
 // Replays the kernel's arithmetic (same tables, same float32 operation order, same index rules) on the host and
 // compares it with the reference chain  crop -> [Resize(fov) -> Resize(res) iff rh > fov_h] -> Resize(obs)
 // (fov_env.py:276-298) evaluated pass by pass in double with the plain per-axis operators.  Also checks the memory
@@ -7,15 +8,17 @@
 // Usage: harness oh ow fh fw antialias          (k_fovea_flexible3 tables) -> "max_err <e> cases <n>" | "unsupported"
 //        harness per oh ow ph pw antialias      (k_fovea_peripheral3 tables + unit_fast over all 256 values)
 //        harness raw oh ow fh fw antialias      (k_fovea_flexible_raw3 tables: raw-crop / mask-out / packed forms)
-//        harness plan oh ow fh fw ph pw antialias resize|raw|mask
+//        harness plan oh ow fh fw ph pw antialias resize|raw|mask [knob=1 ...]
 //                                               which kernel form agx_create + the launch code select for each kind, and why
-//        harness k1plan obs                     which K1 ingest form each screen layout selects at obs x obs, and what it branches on
+//        harness k1plan obs [knob=1 ...]        which K1 ingest form each screen layout selects at obs x obs, and what it branches on
+//        knob: generic flex_v2 per_v2 no_full - the context's fallback knobs (agx_plan.h: Knobs); none given = none set
 //        harness k1tables obs                   the K1 tables of build_k1: x0 x1 a0 a1 y0 y1 b0 b1 and the source-row list
 #include <cstdio>
 #include <cstdlib>
 #include <random>
+#include <string>
 
-#include "agx_host_tables.h"
+#include "agx_plan.h"
 
 using namespace agx;
 using namespace agx::rows;
@@ -189,116 +192,25 @@ static int raw_main(int argc, char **argv) {
 }
 
 // ---- plan report: the kernel form agx_create and the launch code of agx_api.hip select for a geometry, per kind.
-// The table builders are the ones agx_create calls (agx_host_tables.h).  The predicates that live only in agx_api.hip are
-// restated here, each under the name it has there; a change to one of them there must be made here too, and the case table
-// of tests/test_geometry_plan_cpu.py is what notices a plan that moved.
-namespace plan {
+// Nothing is restated here: the table builders are the ones agx_create calls (agx_host_tables.h) and the plans come from the
+// functions agx_create stores in the context and the launch code switches on (agx_plan.h).  The case table of
+// tests/test_geometry_plan_cpu.py is what notices a plan that moved.
 
-constexpr size_t kMaxLds = 160 * 1024;                     // agx_api.hip: kMaxLds
-
-int tap_bucket(int n) { return n <= 2 ? 2 : n <= 4 ? 4 : n <= 8 ? 8 : n <= 12 ? 12 : n <= 16 ? 16 : n; }   // agx_api.hip: tap_bucket
-
-// agx_api.hip: axis_taps - the bucketed tap bound `maxt` only (the same index arithmetic, the weights left out)
-int axis_maxt(int n_in, int n_out, bool antialias) {
-    const double scale = (double)n_in / (double)n_out;
-    const bool aa = antialias && n_in > n_out;
-    int maxt = 1;
-    for (int i = 0; i < n_out; ++i) {
-        int n;
-        if (aa) {
-            const double support = scale, center = scale * (i + 0.5);
-            long long xmin = (long long)(center - support + 0.5);
-            if (xmin < 0) xmin = 0;
-            long long xmax = (long long)(center + support + 0.5);
-            if (xmax > n_in) xmax = n_in;
-            n = xmax > xmin ? (int)(xmax - xmin) : 0;
-        } else {
-            double f = scale * (i + 0.5) - 0.5;
-            if (f < 0.0) f = 0.0;
-            int i0 = (int)f;
-            if (i0 > n_in - 1) i0 = n_in - 1;
-            n = i0 < n_in - 1 ? 2 : 1;
-        }
-        maxt = std::max(maxt, n);
+// trailing `knob=1` arguments (generic, flex_v2, per_v2, no_full) from argv[from] on; false on anything else
+static bool parse_knobs(int argc, char **argv, int from, Knobs &k) {
+    for (int i = from; i < argc; ++i) {
+        const char *eq = strchr(argv[i], '=');
+        if (!eq) return false;
+        const std::string name(argv[i], (size_t)(eq - argv[i]));
+        int *dst = name == "generic" ? &k.generic : name == "flex_v2" ? &k.flex_v2 : name == "per_v2" ? &k.per_v2
+                   : name == "no_full" ? &k.no_full : nullptr;
+        if (!dst) return false;
+        *dst = atoi(eq + 1);
     }
-    return tap_bucket(maxt);
+    return true;
 }
 
-size_t per2_tables(const agx_config &c) {                  // agx_api.hip: per2_tables
-    const int m1 = axis_maxt(c.obs_h, c.per_h, c.antialias != 0), m3 = axis_maxt(c.per_h, c.obs_h, c.antialias != 0);
-    return (size_t)c.per_h * (sizeof(int2) + m1 * sizeof(float)) + (size_t)c.obs_h * (sizeof(int2) + m3 * sizeof(float));
-}
-
-size_t per2_lds(const agx_config &c) {                     // agx_api.hip: per2_lds
-    const size_t raw = ((size_t)c.obs_h * c.obs_w + 15) & ~(size_t)15;
-    const size_t ac = (std::max((size_t)c.obs_h * c.per_w, (size_t)c.per_h * c.obs_w) + 3) & ~(size_t)3;
-    const size_t b = ((size_t)c.per_h * c.per_w + 3) & ~(size_t)3;
-    return 1024 + raw + (ac + b) * sizeof(float) + per2_tables(c);
-}
-
-// agx_api.hip: build_family(...).floats[r] - LDS floats of the staged table of window size r
-size_t family_floats(int which, int r, int fov, int obs, bool antialias) {
-    const int n_in = which == 0 ? r : (which == 1 ? fov : r);
-    const int n_out = which == 0 ? fov : (which == 1 ? r : obs);
-    const int maxt = axis_maxt(n_in, n_out, antialias);
-    return (((size_t)2 * n_out + (size_t)n_out * maxt) + 3) & ~(size_t)3;
-}
-
-size_t flex_tab_floats(const agx_config &c) {              // agx_api.hip: agx_create, ctx->flex_tab_floats
-    const bool aa = c.antialias != 0;
-    size_t worst_w = 0, worst_h = 0;
-    for (int r = 1; r <= c.obs_w; ++r) {
-        size_t s = 0;
-        for (int k = 0; k < 3; ++k) s += family_floats(k, r, c.fov_w, c.obs_w, aa);
-        worst_w = std::max(worst_w, s);
-    }
-    for (int r = 1; r <= c.obs_h; ++r) {
-        size_t s = 0;
-        for (int k = 0; k < 3; ++k) s += family_floats(k, r, c.fov_h, c.obs_h, aa);
-        worst_h = std::max(worst_h, s);
-    }
-    return worst_w + worst_h;
-}
-
-size_t flex2_lds(const agx_config &c, size_t tab_floats) { // agx_api.hip: flex2_lds
-    const size_t raw = ((size_t)c.obs_h * c.obs_w + 15) & ~(size_t)15;
-    const size_t ae = (std::max((size_t)c.obs_h * c.fov_w, (size_t)c.fov_h * c.obs_w) + 3) & ~(size_t)3;
-    const size_t b = ((size_t)c.fov_h * c.fov_w + 3) & ~(size_t)3;
-    const size_t cc = ((size_t)c.fov_h * c.obs_w + 3) & ~(size_t)3;
-    return 1024 + std::max(raw, cc * sizeof(float)) + (ae + b + tab_floats) * sizeof(float);
-}
-
-size_t fixed_lds(const agx_config &c) {                    // agx_api.hip: fixed_lds
-    const size_t raw = ((size_t)c.fov_h * c.obs_w + 15) & ~(size_t)15;
-    size_t b = raw;
-    if (c.out_mode == AGX_OUT_RESIZE) b += (size_t)c.obs_h * sizeof(Tap) + (size_t)c.fov_h * c.obs_w * sizeof(float);
-    return b;
-}
-
-size_t generic_buf1(const agx_config &c) {                 // agx_api.hip: generic_buf1
-    const size_t cap = ((size_t)c.obs_h * c.obs_w + 3) & ~(size_t)3;
-    if (c.kind != AGX_KIND_PERIPHERAL) return cap;
-    const size_t abc = (size_t)c.obs_h * c.per_w + (size_t)c.per_h * c.per_w + (size_t)c.per_h * c.obs_w;
-    return (abc + 3) & ~(size_t)3;
-}
-
-size_t generic_lds(const agx_config &c) {                  // agx_api.hip: generic_lds
-    const size_t cap = ((size_t)c.obs_h * c.obs_w + 3) & ~(size_t)3;
-    int tmax = std::max(std::max(c.obs_h, c.obs_w), std::max(c.fov_h, c.fov_w));
-    if (c.kind == AGX_KIND_PERIPHERAL) tmax = std::max(tmax, std::max(c.per_h, c.per_w));
-    return (cap + generic_buf1(c)) * sizeof(float) + (size_t)tmax * sizeof(Tap);
-}
-
-// agx_api.hip: agx_create, "the LDS of the kernel that will actually run" (no knob set).  0 = accepted, else the bytes in
-// the message "geometry needs %zu B of LDS per workgroup (limit %zu)"
-size_t create_refusal(const agx_config &c) {
-    const bool per_tuned = per2_lds(c) <= kMaxLds && c.per_w <= kThreads;
-    const size_t lds = c.kind == AGX_KIND_FIXED ? fixed_lds(c)
-                       : (c.kind == AGX_KIND_PERIPHERAL && per_tuned ? per2_lds(c) : generic_lds(c));
-    return lds > kMaxLds ? lds : 0;
-}
-
-void print_set(const char *key, const std::vector<int2> &meta, int from, int to) {
+static void print_set(const char *key, const std::vector<int2> &meta, int from, int to) {
     bool has[17] = {};
     for (int r = from; r <= to; ++r) has[meta[r].x] = true;
     printf(" %s=", key);
@@ -308,98 +220,73 @@ void print_set(const char *key, const std::vector<int2> &meta, int from, int to)
     if (!any) printf("-");
 }
 
-// why a composed-operator plan (build_flex3 / build_flexraw) does not apply: their entry guards restated, everything
-// behind the guards is a tap bound (a bucket overflows, or an up-scale row has more taps than the kernel's 2 or 3)
-const char *composed_refusal(const agx_config &c, bool ok, size_t lds) {
-    if (c.obs_w > kThreads) return "obs_w>256";
-    if (c.fov_h > kThreads / 8) return "fov_h>32";
-    if (c.obs_h > 1024) return "obs_h>1024";
-    if (!ok) return "taps";
-    if (lds > kMaxLds) return "lds";
-    return nullptr;
+// agx_create's LDS check: 0 = accepted, else the bytes in "geometry needs %zu B of LDS per workgroup (limit %zu)"
+static size_t create_refusal(const agx_config &c, const Knobs &k) {
+    const size_t lds = create_lds(c, k);
+    return lds > kMaxLds ? lds : 0;
 }
 
-// agx_fovea_flexible / agx_fovea_flexible_packed behind a refused composed plan
-const char *flex_fallback(const agx_config &c, size_t *lds) {
-    const size_t lds2 = flex2_lds(c, flex_tab_floats(c));
-    if (lds2 <= kMaxLds) { *lds = lds2; return "flexible2"; }
-    *lds = generic_lds(c);
-    return "generic";
-}
-
-int run(int argc, char **argv) {
+static int plan_main(int argc, char **argv) {
     if (argc < 10) return 2;
     agx_config c{};
     c.obs_h = atoi(argv[2]); c.obs_w = atoi(argv[3]); c.fov_h = atoi(argv[4]); c.fov_w = atoi(argv[5]);
     c.per_h = atoi(argv[6]); c.per_w = atoi(argv[7]); c.antialias = atoi(argv[8]);
     const char *mode = argv[9];
     const int out_mode = !strcmp(mode, "resize") ? AGX_OUT_RESIZE : !strcmp(mode, "mask") ? AGX_OUT_MASK : !strcmp(mode, "raw") ? AGX_OUT_RAW : -1;
-    if (out_mode < 0) return 2;
-    const bool headline = c.obs_h == 84 && c.obs_w == 84 && c.fov_h == 30 && c.fov_w == 30;
+    Knobs k;
+    if (out_mode < 0 || !parse_knobs(argc, argv, 10, k)) return 2;
     size_t refused;
     // ---- fixed (agx_fovea_fixed)
     c.kind = AGX_KIND_FIXED;
     c.out_mode = out_mode;
-    if ((refused = create_refusal(c))) printf("fixed form=refused lds=%zu\n", refused);
-    else printf("fixed form=%s lds=%zu\n", headline ? "fixed<GeomS>" : "fixed<GeomR>", fixed_lds(c));
+    if ((refused = create_refusal(c, k))) printf("fixed form=refused lds=%zu\n", refused);
+    else {
+        const FovPlan p = plan_fixed(c);
+        printf("fixed form=%s lds=%zu\n", p.headline ? "fixed<GeomS>" : "fixed<GeomR>", p.lds);
+    }
     // ---- flexible (agx_fovea_flexible, agx_fovea_flexible_packed)
     c.kind = AGX_KIND_FLEXIBLE;
-    if ((refused = create_refusal(c))) printf("flexible form=refused lds=%zu\n", refused);
-    else if (out_mode == AGX_OUT_RESIZE) {
-        const Flex3Host h = build_flex3(c);
-        const size_t lds3 = h.ok ? flex3_lds(h, c) : 0;
-        const char *why = composed_refusal(c, h.ok, lds3);
-        if (!why) {
-            printf("flexible form=flex3");
-            print_set("W", h.wc_meta, 1, c.obs_w);
-            print_set("H", h.hd_meta, c.fov_h + 1, c.obs_h);
-            printf(" rstep=%d lds=%zu\n", kThreads / c.obs_w, lds3);
-        } else {
-            size_t lds = 0;
-            const char *form = flex_fallback(c, &lds);
-            printf("flexible form=%s why=%s lds=%zu\n", form, why, lds);
-        }
-    } else {
-        const FlexRawHost h = build_flexraw(c);
-        const size_t ldsr = h.ok ? h.lds(c) : 0;
-        const char *why = composed_refusal(c, h.ok, ldsr);
-        if (!why) {
-            printf("flexible form=raw3");
-            print_set("W", h.wb_meta, 1, c.obs_w);
-            print_set("H", h.hd_meta, c.fov_h + 1, c.obs_h);
-            printf(" rstep=%d lds=%zu packed=raw3\n", kThreads / c.obs_w, ldsr);
-        } else {
-            size_t lds = 0;
-            const char *form = flex_fallback(c, &lds);
-            printf("flexible form=%s why=%s lds=%zu packed=offsets+%s\n", form, why, lds, form);
-        }
+    if ((refused = create_refusal(c, k))) printf("flexible form=refused lds=%zu\n", refused);
+    else {
+        const Flex3Host f3 = build_flex3(c);
+        const FlexRawHost fr = build_flexraw(c);
+        HostFamily fam[6];
+        const FovPlan p = plan_flexible(c, k, f3, fr, build_families(c, fam));
+        const char *form = p.form == kFormFlex3 ? "flex3" : p.form == kFormRaw3 ? "raw3" : p.form == kFormFlexible2 ? "flexible2" : "generic";
+        printf("flexible form=%s", form);
+        if (!p.why) {
+            print_set("W", p.form == kFormFlex3 ? f3.wc_meta : fr.wb_meta, 1, c.obs_w);
+            print_set("H", p.form == kFormFlex3 ? f3.hd_meta : fr.hd_meta, c.fov_h + 1, c.obs_h);
+            printf(" rstep=%d lds=%zu", kThreads / c.obs_w, p.lds);
+        } else
+            printf(" why=%s lds=%zu", p.why, p.lds);
+        if (p.packed == kPackedRaw3) printf(" packed=raw3");
+        else if (p.packed != kPackedNone) printf(" packed=offsets+%s", p.packed == kPackedOffsetsFlexible2 ? "flexible2" : "generic");
+        printf("\n");
     }
     // ---- peripheral (agx_fovea_peripheral): always resize_to_full (pipeline.py, fov_env.py:361-364)
     c.kind = AGX_KIND_PERIPHERAL;
     c.out_mode = AGX_OUT_RESIZE;
     if (c.per_h < 1 || c.per_w < 1) printf("peripheral form=none\n");
-    else if ((refused = create_refusal(c))) printf("peripheral form=refused lds=%zu\n", refused);
+    else if ((refused = create_refusal(c, k))) printf("peripheral form=refused lds=%zu\n", refused);
     else {
-        const Per3Host h = build_per3(c);
-        const int same = (c.per_h == c.obs_h && c.per_w == c.obs_w) ? 1 : 0;
-        if (h.ok && h.lds <= kMaxLds) printf("peripheral form=per3 mt=%d same=%d lds=%zu\n", h.mt, same, h.lds);
-        else {
-            const char *why = h.ok ? "lds" : (c.obs_w > kThreads ? "obs_w>256" : c.per_w > kThreads ? "per_w>256" : c.per_h > 256 ? "per_h>256" : "taps");
-            if (per2_lds(c) <= kMaxLds && c.per_w <= kThreads) {
-                const bool aa = c.antialias != 0;
-                const int m0 = axis_maxt(c.obs_w, c.per_w, aa), m1 = axis_maxt(c.obs_h, c.per_h, aa);
-                printf("peripheral form=peripheral2 mt=%d same=%d why=%s lds=%zu\n", m0 == m1 && m0 <= 16 ? m0 : 0, same, why, per2_lds(c));
-            } else
-                printf("peripheral form=generic same=%d why=%s lds=%zu\n", same, why, generic_lds(c));
+        int nin[4], nout[4], maxt[4];
+        per_axes(c, nin, nout);
+        for (int a = 0; a < 4; ++a) {
+            std::vector<int2> ln;
+            std::vector<float> w;
+            axis_taps(nin[a], nout[a], c.antialias != 0, ln, w, maxt[a]);
         }
+        const FovPlan p = plan_peripheral(c, k, build_per3(c), maxt);
+        if (p.form == kFormPer3) printf("peripheral form=per3 mt=%d same=%d lds=%zu\n", p.mt, p.same, p.lds);
+        else if (p.form == kFormPeripheral2) printf("peripheral form=peripheral2 mt=%d same=%d why=%s lds=%zu\n", p.mt, p.same, p.why, p.lds);
+        else printf("peripheral form=generic same=%d why=%s lds=%zu\n", p.same, p.why, p.lds);
     }
     return 0;
 }
 
-}  // namespace plan
-
-// ---- K1 ingest: the plan build_k1 (agx_host_tables.h) hands agx_create, per screen layout, as the launch code of
-// agx_api.hip reads it with no knob set (agx_ingest, agx_ingest_gray_raw, ingest_compact: k1_band12 at plan.band_rows).
+// ---- K1 ingest: the plan build_k1 (agx_host_tables.h) hands agx_create, per screen layout, as plan_k1 (agx_plan.h) turns it
+// into the launch agx_ingest, agx_ingest_gray_raw and ingest_compact make at plan.band_rows.
 //   form=band12 br=12 bands=B
 //   form=general br=R bands=B partial=P affine=A xclamp=X yclamp=Y
 // partial: the last band has fewer rows than br; affine: source rows from the integer form (whole screens only - compact
@@ -408,6 +295,8 @@ static int k1plan_main(int argc, char **argv) {
     if (argc < 3) return 2;
     const int o = atoi(argv[2]);
     if (o < 4 || o > 1024 || (o & 3)) return 2;             // not a size agx_create accepts (k1tables: the same)
+    Knobs knobs;
+    if (!parse_knobs(argc, argv, 3, knobs)) return 2;
     const K1Host h = build_k1(o, o);
     const K1Plan &q = h.plan;
     bool xclamp = false, yclamp = false;
@@ -415,14 +304,13 @@ static int k1plan_main(int argc, char **argv) {
         xclamp = xclamp || h.x0[i] == h.x1[i];
         yclamp = yclamp || h.y0[i] == h.y1[i];
     }
-    const int br = q.band_rows, bands = (o + br - 1) / br;
-    const char *names[4] = {"rgb", "gray", "rgb-compact", "gray-compact"};
+    const char *names[4] = {"rgb", "gray", "rgb-compact", "gray-compact"};      // K1Layout
     for (int k = 0; k < 4; ++k) {
-        const bool compact = k >= 2;
-        if (k1_band12(q, compact, br)) printf("%s form=band12 br=%d bands=%d\n", names[k], br, bands);
+        const K1Launch l = plan_k1(q, k, q.band_rows, o, o, knobs);
+        if (l.band12) printf("%s form=band12 br=%d bands=%d\n", names[k], l.band_rows, l.nbands);
         else
-            printf("%s form=general br=%d bands=%d partial=%d affine=%d xclamp=%d yclamp=%d\n", names[k], br, bands, o % br != 0,
-                   !compact && q.y_affine, xclamp, yclamp);
+            printf("%s form=general br=%d bands=%d partial=%d affine=%d xclamp=%d yclamp=%d\n", names[k], l.band_rows, l.nbands,
+                   o % l.band_rows != 0, k < kK1RgbCompact && q.y_affine, xclamp, yclamp);
     }
     printf("affine mul=%d add=%d shift=%d ok=%d\n", q.y_mul, q.y_add, q.y_shift, q.y_affine);
     printf("flags adjacent=%d pairs=%d band12_ok=%d compact12_ok=%d rows=%d\n", q.adjacent, q.pairs, q.band12_ok, q.compact12_ok,
@@ -451,7 +339,7 @@ static int k1tables_main(int argc, char **argv) {
 int main(int argc, char **argv) {
     if (argc > 1 && !strcmp(argv[1], "k1plan")) return k1plan_main(argc, argv);
     if (argc > 1 && !strcmp(argv[1], "k1tables")) return k1tables_main(argc, argv);
-    if (argc > 1 && !strcmp(argv[1], "plan")) return plan::run(argc, argv);
+    if (argc > 1 && !strcmp(argv[1], "plan")) return plan_main(argc, argv);
     if (argc > 1 && !strcmp(argv[1], "per")) return per_main(argc, argv);
     if (argc > 1 && !strcmp(argv[1], "raw")) return raw_main(argc, argv);
     if (argc < 6) return 2;

@@ -1,8 +1,10 @@
 """The case table of tests/test_gpu_geometry.py (tests/golden/geometry_cases.json) pinned to the kernel form each case
-selects.  agx_create and the launch code pick a kernel form from the geometry alone; `host_tables_harness plan` restates
-that choice on the CPU from the very table builders agx_create calls (active-gym_amd/csrc/agx_host_tables.h).  If a bucket,
-a tap bound or an LDS bound is retuned, a label here goes red and the table has to be chosen again - instead of the GPU
-cases silently moving to another kernel.  The coverage test says which forms the table as a whole has to reach.
+selects.  agx_create picks a kernel form from the geometry (and the context's fallback knobs) alone and the launch code
+switches on the stored plan; `host_tables_harness plan` prints that plan on the CPU from the very functions agx_create calls
+(active-gym_amd/csrc/agx_plan.h over the table builders of agx_host_tables.h) - nothing is restated.  If a bucket, a tap
+bound or an LDS bound is retuned, or the library's dispatch drifts, a label here goes red and the table has to be chosen
+again - instead of the GPU cases silently moving to another kernel.  The coverage test says which forms the table as a whole
+has to reach; the knob tests pin what the fallback comparisons of tests/test_gpu_parity.py assume a knob selects.
 No GPU involved: hipcc compiles the harness as a plain host program."""
 import json
 import os
@@ -35,9 +37,9 @@ def harness(tmp_path_factory):
     return out
 
 
-def plan(harness, c, mode):
-    """{kind: label} of `harness plan` for the case's geometry in output mode `mode`."""
-    r = subprocess.run([harness, "plan", *map(str, (*c["obs"], *c["fov"], *c["per"], c["aa"], mode))],
+def plan(harness, c, mode, *knobs):
+    """{kind: label} of `harness plan` for the case's geometry in output mode `mode`, with the knobs ("generic=1", ...) set."""
+    r = subprocess.run([harness, "plan", *map(str, (*c["obs"], *c["fov"], *c["per"], c["aa"], mode)), *knobs],
                        capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stdout + r.stderr
     out = {}
@@ -166,3 +168,53 @@ def test_every_form_has_one_case_with_the_16_bit_and_colour_checks():
     forms = {form(k, v) for c, a, k, v in _entries() if not v.startswith("refused")}
     with_extras = {form(k, v) for c, a, k, v in _entries() if c["extras"] and not v.startswith("refused")}
     assert forms - with_extras == set()
+
+
+# ---- the fallback knobs (agx_plan.h: Knobs; AGX_FOVEA_GENERIC, AGX_FLEX_V2, AGX_PER_V2 in the library)
+def _form(label):
+    return label.split(" ", 1)[0]
+
+
+def _with_knob(harness, knob):
+    """(key, kind, label without a knob, label with it) of every entry of the case table."""
+    out = []
+    for c in CASES:
+        got = {mode: plan(harness, c, mode, knob) for mode in {MODES[k][1] for k in c["plan"]}}
+        for key, want in c["plan"].items():
+            kind, mode = MODES[key]
+            out.append((key, kind, want, got[mode][kind]))
+    return out
+
+
+def test_generic_knob_sends_every_flexible_and_peripheral_entry_to_the_generic_kernel(harness):
+    seen = 0
+    for key, kind, want, got in _with_knob(harness, "generic=1"):
+        if kind == "fixed":
+            assert got == want, key
+        elif not got.startswith("refused"):
+            assert _form(got) == "generic", (key, got)
+            assert "packed=" not in got or got.endswith("packed=offsets+generic"), (key, got)
+            seen += 1
+    assert seen >= 20
+
+
+def test_flex_v2_knob_leaves_no_composed_flexible_form(harness):
+    seen = 0
+    for key, kind, want, got in _with_knob(harness, "flex_v2=1"):
+        if kind == "flexible":
+            assert _form(got) not in ("flex3", "raw3") and "packed=raw3" not in got, (key, got)
+            seen += _form(want) in ("flex3", "raw3")
+        else:
+            assert got == want, key
+    assert seen >= 10
+
+
+def test_per_v2_knob_leaves_no_per3(harness):
+    seen = 0
+    for key, kind, want, got in _with_knob(harness, "per_v2=1"):
+        if kind == "peripheral":
+            assert _form(got) != "per3", (key, got)
+            seen += _form(want) == "per3"
+        else:
+            assert got == want, key
+    assert seen >= 5

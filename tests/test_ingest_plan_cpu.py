@@ -1,7 +1,7 @@
 """The case table of tests/test_gpu_ingest_geometry.py (tests/golden/ingest_cases.json) pinned to the K1 ingest form each
 obs_size selects, per screen layout.  agx_create picks the K1 form from obs_size alone (build_k1,
-active-gym_amd/csrc/agx_host_tables.h); `host_tables_harness k1plan` reports that plan from the very function agx_create
-calls, `k1tables` the tables it uploads.  If band_rows or the band12 condition is retuned, a label here goes red and the
+active-gym_amd/csrc/agx_host_tables.h; plan_k1, agx_plan.h); `host_tables_harness k1plan` reports that plan from the very
+functions agx_create calls, `k1tables` the tables it uploads.  If band_rows or the band12 condition is retuned, a label here goes red and the
 table has to be chosen again - instead of the GPU cases silently moving to another kernel.  The coverage test says what the
 table as a whole has to reach; the exhaustive tests hold the tables of all 256 legal sizes against the oracle's OpenCV
 restatement and re-derive every claim the plan makes (affine rows, band12 read bound, packed row pairs) in Python.
@@ -40,16 +40,16 @@ def harness(tmp_path_factory):
     return out
 
 
-def _lines(harness, cmd, obs):
-    r = subprocess.run([harness, cmd, str(obs)], capture_output=True, text=True, timeout=300)
+def _lines(harness, cmd, obs, *knobs):
+    r = subprocess.run([harness, cmd, str(obs), *knobs], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stdout + r.stderr
     return [line.split(" ") for line in r.stdout.strip().splitlines()]
 
 
-def k1plan(harness, obs):
-    """({layout: label}, {key: int} of the `affine` and `flags` lines) of `harness k1plan obs`."""
+def k1plan(harness, obs, *knobs):
+    """({layout: label}, {key: int} of the `affine` and `flags` lines) of `harness k1plan obs`, with the knobs ("no_full=1") set."""
     labels, facts = {}, {}
-    for words in _lines(harness, "k1plan", obs):
+    for words in _lines(harness, "k1plan", obs, *knobs):
         if words[0] in LAYOUTS:
             assert words[1].startswith("form=")
             labels[words[0]] = " ".join(words[1:])[len("form="):]
@@ -225,7 +225,7 @@ def test_plan_claims_hold_for_all_256_sizes(plans, tables):
         if f["band12_ok"] or f["compact12_ok"]:
             n_band12 += 1
             assert f["band12_ok"] and f["ok"] and f["adjacent"] and o % 12 == 0 and (o // 4) * 12 <= 256, o
-            # the band12 workgroup's LDS (band12_lds, agx_api.hip; layout in agx_k1_ingest.h): ytab12[12] int2 | xtab12[ow] int2 |
+            # the band12 workgroup's LDS (band12_lds, agx_plan.h; layout in agx_k1_ingest.h): ytab12[12] int2 | xtab12[ow] int2 |
             # gray u16 [2 frames][12 rows][top, bottom][160] | 8 bytes of slack.  Phase 2 reads two aligned dwords at byte
             # (2 x0) & ~3 of a gray row; for the last row of the last frame that read has to end inside the allocation.
             tabs, row_b = 8 * (12 + o), 2 * RAW_W
@@ -236,3 +236,18 @@ def test_plan_claims_hold_for_all_256_sizes(plans, tables):
             assert lds <= 64 * 1024
             assert f["compact12_ok"] == int(pairs), o
     assert n_affine == len([o for o in SIZES if 40 <= o <= 208]) and n_band12 == 4
+
+
+def test_no_full_knob_leaves_no_band12_at_the_tables_sizes(harness, plans):
+    """AGX_INGEST_NO_FULL (agx_plan.h: Knobs::no_full): the general band kernel at every size of the case table, in every
+    layout, with the band height and band count the plan has without the knob."""
+    band12 = 0
+    for o in sorted({c["obs"] for c in CASES}):
+        labels, facts = k1plan(harness, o, "no_full=1")
+        assert facts == plans[o][1], o
+        for lay in LAYOUTS:
+            assert labels[lay].startswith("general "), (o, lay, labels[lay])
+            want = plans[o][0][lay]
+            assert (_field(labels[lay], "br"), _field(labels[lay], "bands")) == (_field(want, "br"), _field(want, "bands")), (o, lay)
+            band12 += want.startswith("band12 ")
+    assert band12 == 16
