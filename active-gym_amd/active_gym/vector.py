@@ -122,6 +122,7 @@ class AtariVecEnv:
     history = None           # history.FrameHistory when args.history_len > 0
     history_len = 0
     _glimpse_of = None       # the history the cached glimpse.GlimpseMemory objects (by glimpses) read
+    _replay_of = None        # the history the cached replay.ReplaySampler objects (by argument tuple) read
 
     def __init__(self, args, num_envs: int, kind: str = "fixed", env_offset: int = 0, noop_fn=None,
                  autoreset: bool = True, noop_per_env: bool = False):
@@ -571,6 +572,23 @@ class AtariVecEnv:
             mem = self._glimpse[int(glimpses)] = GlimpseMemory(self.history, glimpses)      # ValueError for a kind or mode that is not served
         obs, _, _ = mem.observe(self._glimpse_env, self.history.last_index(), out=out)
         return self._out(obs)
+
+    def replay_sampler(self, back: int = 0, forward: int = 1, attempts: int = 16, seed: Optional[int] = None):
+        """A replay.ReplaySampler on the env's frame history, cached per argument tuple: ``sample(B)`` draws (env, index) pairs
+        that are retained, have ``back`` valid earlier glimpses of their episode and ``forward`` later appends of it, and
+        ``transitions(B)`` re-creates both observations (index and index + forward never straddle a reset).  ``seed=None``
+        takes ``args.seed``.  Needs ``history_len`` > 0: ValueError otherwise."""
+        from .replay import ReplaySampler
+        if self.history is None:
+            raise ValueError("replay_sampler needs a frame history (AtariEnvArgs.history_len > 0)")
+        if self._replay_of is not self.history:                 # a rebuilt pipeline (rekind) has a new history
+            self._replay_of, self._replay = self.history, {}
+        seed = int(getattr(self.args, "seed", 0) or 0) if seed is None else int(seed)
+        key = (int(back), int(forward), int(attempts), seed)
+        smp = self._replay.get(key)
+        if smp is None:
+            smp = self._replay[key] = ReplaySampler(self.history, back, forward, attempts, seed)
+        return smp
 
     def _next_stage(self):
         st = getattr(self, "_stage", None)
