@@ -70,12 +70,29 @@ SIGNATURES = {
 }
 
 _lib = None
+_bound = []             # (library, table) pairs bind() has done
 
 
 class AgxError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__(f"libagx error {code}: {msg}")
         self.code = code
+
+
+def bind(handle, signatures):
+    """Set restype / argtypes of every entry of a SIGNATURES table on a loaded library, once per (library, table); returns the
+    library.  AttributeError if the .so does not export a name."""
+    if not any(h is handle and s is signatures for h, s in _bound):
+        for name, (res, args) in signatures.items():
+            try:
+                fn = getattr(handle, name)       # AttributeError if the .so does not export it
+            except AttributeError:
+                if os.environ.get("AGX_LIB") and name == "agx_step_flexible_packed":
+                    continue                     # an older diagnostic build selected by hand (tools/canary_probe.py's r3bug library)
+                raise
+            fn.restype, fn.argtypes = res, args
+        _bound.append((handle, signatures))
+    return handle
 
 
 def lib():
@@ -88,16 +105,7 @@ def lib():
         raise ImportError(
             f"{path} not found: the HIP extension is not built (run `python active-gym_amd/build.py`). "
             "active_gym has no CPU fallback for the observation path.")
-    handle = C.CDLL(path)
-    for name, (res, args) in SIGNATURES.items():
-        try:
-            fn = getattr(handle, name)       # AttributeError if the .so does not export it
-        except AttributeError:
-            if os.environ.get("AGX_LIB") and name == "agx_step_flexible_packed":
-                continue                     # an older diagnostic build selected by hand (tools/canary_probe.py's r3bug library)
-            raise
-        fn.restype = res
-        fn.argtypes = args
+    handle = bind(C.CDLL(path), SIGNATURES)
     v = handle.agx_abi_version()
     if v != ABI_VERSION:
         raise ImportError(f"{path}: ABI version {v}, binding expects {ABI_VERSION}")

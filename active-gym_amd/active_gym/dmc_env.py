@@ -18,12 +18,12 @@ from concurrent.futures import ThreadPoolExecutor
 from typing import Optional, Sequence, Tuple
 
 import numpy as np
-import torch
 
 from . import _native as nat
 from .atari_env import _SingleEnv
 from .spaces import Box
-from .vector import AtariVecEnv
+from .staging import Staging
+from .vector import AtariVecEnv, wants_packed
 
 
 class DMCEnvArgs:
@@ -205,15 +205,9 @@ class DMCVecEnv(AtariVecEnv):
     def _setup_source(self, args, noop_fn, env_offset):
         h, w = self.obs_size
         shape = (self.num_envs, h, w, 3)
-        self._h_frames = torch.empty(shape, dtype=torch.uint8, pin_memory=True)
-        self._d_frames = torch.empty(shape, dtype=torch.uint8, device=self.device)
-        self._h_rframes = torch.empty(shape, dtype=torch.uint8, pin_memory=True)
-        self._h_rcmd = torch.empty((self.num_envs,), dtype=torch.uint8, pin_memory=True)
-        self._h_cmd = torch.empty((self.num_envs,), dtype=torch.uint8, pin_memory=True)
-        self._d_cmd = torch.empty((self.num_envs,), dtype=torch.uint8, device=self.device)
-        self._ev_copy = torch.cuda.Event()
-        self._alloc_reset_buffers()
-        self.runner = DMCHostRunner(args, self.num_envs, self._h_frames.numpy(), workers=getattr(args, "num_workers", None),
+        # one set, no copy stream: a reset render is the env's whole buffer
+        self._staging = Staging(self.num_envs, shape, shape, reset_slot0=False, doubled=False, device=self.device)
+        self.runner = DMCHostRunner(args, self.num_envs, self._staging.h_frames.numpy(), workers=getattr(args, "num_workers", None),
                                     env_offset=env_offset)
         mode = getattr(args, "gray_mode", "cv15")
         if mode not in ("cv15", "cv14"):
@@ -223,7 +217,7 @@ class DMCVecEnv(AtariVecEnv):
     def _resolve_channels(self, args):
         if getattr(args, "grey", True):
             return 1
-        if getattr(args, "ragged_obs", "padded") == "packed":
+        if wants_packed(args):
             raise ValueError("grey=False with ragged_obs='packed': the packed ragged crops are gray only")
         return 3
 
@@ -232,13 +226,7 @@ class DMCVecEnv(AtariVecEnv):
 
     def _ingest(self, cmd=None):
         mode = nat.GRAY_NONE if self.channels == 3 else self._gray_mode
-        self.pipe.ingest_rgb(self._d_frames, self._d_cmd if cmd is None else cmd, mode)
-
-    def _h_reset_rows(self, buf=None):
-        return self._h_rframes if buf is None else buf
-
-    def _d_reset_target(self):
-        return self._d_frames
+        self.pipe.ingest_rgb(self._staging.d_frames, self._staging.d_cmd if cmd is None else cmd, mode)
 
     def _extra_info(self, info):                                                               # dmc_env.py:189-192
         info["internal_state"] = np.stack([np.asarray(s) for s in self.runner.internal_state])

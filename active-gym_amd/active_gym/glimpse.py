@@ -27,18 +27,10 @@ GLIMPSE_LIMIT = 8                     # AGX_GLIMPSE_LIMIT
 SIGNATURES = {
     "agx_history_observe_memory": (C.c_int, [_P, C.c_int32, _P, _P, C.c_int32, _P, _P, _P, _P]),
 }
-_bound = False
 
 
 def lib():
-    global _bound
-    handle = nat.lib()
-    if not _bound:
-        for name, (res, args) in SIGNATURES.items():
-            fn = getattr(handle, name)           # AttributeError if the .so does not export it
-            fn.restype, fn.argtypes = res, args
-        _bound = True
-    return handle
+    return nat.bind(nat.lib(), SIGNATURES)
 
 
 def check_glimpse_source(kind: str, out_mode: int) -> None:

@@ -36,18 +36,10 @@ SIGNATURES = {
     "agx_history_observe": (C.c_int, [_P, C.c_int, _P, _P, C.c_int32, _P, C.c_int, _P, _P, _P, _P]),
     "agx_loop_set_history": (C.c_int, [_P, _P]),
 }
-_bound = False
 
 
 def lib():
-    global _bound
-    handle = nat.lib()
-    if not _bound:
-        for name, (res, args) in SIGNATURES.items():
-            fn = getattr(handle, name)           # AttributeError if the .so does not export it
-            fn.restype, fn.argtypes = res, args
-        _bound = True
-    return handle
+    return nat.bind(nat.lib(), SIGNATURES)
 
 
 def check_env_history(kind: str, history_len, channels: int = 1, ragged_obs: str = "padded") -> int:

@@ -27,18 +27,10 @@ SIGNATURES = {
     "agx_loop_host_wait": (C.c_int, [_P]),
     "agx_loop_host_final": (C.c_int, [_P, C.POINTER(_P), C.POINTER(_P), C.POINTER(_P)]),
 }
-_bound = False
 
 
 def lib():
-    global _bound
-    handle = nat.lib()
-    if not _bound:
-        for name, (res, args) in SIGNATURES.items():
-            fn = getattr(handle, name)           # AttributeError if the .so does not export it
-            fn.restype, fn.argtypes = res, args
-        _bound = True
-    return handle
+    return nat.bind(nat.lib(), SIGNATURES)
 
 
 def partition(num_envs: int, chunks: int):

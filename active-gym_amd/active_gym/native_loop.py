@@ -44,18 +44,10 @@ SIGNATURES = {
     "agx_loop_step": (C.c_int, [_P, _P, _P, C.c_int, _P, _P, _P, _P, C.POINTER(AgxLoopResult), _P]),
     "agx_loop_reset_envs": (C.c_int, [_P, _P, C.c_int32, _P, _P, _P, _P, _P]),
 }
-_bound = False
 
 
 def _lib():
-    global _bound
-    lib = nat.lib()
-    if not _bound:
-        for name, (res, args) in SIGNATURES.items():
-            fn = getattr(lib, name)           # AttributeError if the .so does not export it
-            fn.restype, fn.argtypes = res, args
-        _bound = True
-    return lib
+    return nat.bind(nat.lib(), SIGNATURES)
 
 
 class _DeviceView:

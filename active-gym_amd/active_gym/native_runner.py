@@ -55,11 +55,7 @@ def lib():
     if _lib is None:
         if not os.path.exists(LIB_PATH):
             raise ImportError(f"{LIB_PATH} not found: run `python active-gym_amd/build.py`")
-        h = C.CDLL(LIB_PATH)
-        for name, (res, args) in SIGNATURES.items():
-            fn = getattr(h, name)
-            fn.restype, fn.argtypes = res, args
-        _lib = h
+        _lib = nat.bind(C.CDLL(LIB_PATH), SIGNATURES)
     return _lib
 
 

@@ -37,18 +37,10 @@ SIGNATURES = {
     "agx_replay_sample": (C.c_int, [_P, C.c_int32, _P, _P, _P, _P, _P]),
     "agx_replay_inspect": (C.c_int, [_P, _P, _P, C.c_int32, _P, _P, _P]),
 }
-_bound = False
 
 
 def lib():
-    global _bound
-    handle = nat.lib()
-    if not _bound:
-        for name, (res, args) in SIGNATURES.items():
-            fn = getattr(handle, name)           # AttributeError if the .so does not export it
-            fn.restype, fn.argtypes = res, args
-        _bound = True
-    return handle
+    return nat.bind(nat.lib(), SIGNATURES)
 
 
 def check_replay_args(back: int, forward: int, attempts: int):

@@ -123,3 +123,27 @@ def test_binding_constants_mirror_the_header():
         assert getattr(nat, name) == int(val, 0), (name, getattr(nat, name), val)
         found += 1
     assert found >= 30
+
+
+def test_bind_names_a_missing_export():
+    """_native.bind: a table with a name the library does not export raises AttributeError that names it, and is not taken for
+    bound: the next call raises again."""
+    from active_gym import _native as nat
+    handle = ctypes.CDLL(_build())
+    table = {"agx_abi_version": (ctypes.c_int, []), "agx_no_such_entry_point": (ctypes.c_int, [])}
+    for _ in range(2):
+        with pytest.raises(AttributeError, match="agx_no_such_entry_point"):
+            nat.bind(handle, table)
+
+
+def test_bind_twice_leaves_the_signatures_as_set():
+    from active_gym import _native as nat
+    handle = ctypes.CDLL(_build())
+    table = {"agx_abi_version": (ctypes.c_int, []), "agx_algorithmic_bytes": (ctypes.c_int64, [ctypes.c_void_p, ctypes.c_int])}
+    assert nat.bind(handle, table) is handle
+    fn = handle.agx_algorithmic_bytes
+    assert fn.restype is ctypes.c_int64 and fn.argtypes == [ctypes.c_void_p, ctypes.c_int]
+    assert nat.bind(handle, table) is handle
+    assert handle.agx_algorithmic_bytes is fn and fn.restype is ctypes.c_int64 and fn.argtypes == [ctypes.c_void_p, ctypes.c_int]
+    assert handle.agx_abi_version.restype is ctypes.c_int and handle.agx_abi_version.argtypes == []
+    assert handle.agx_abi_version() == nat.ABI_VERSION

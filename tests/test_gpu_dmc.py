@@ -199,3 +199,62 @@ def test_dmc_spaces_non_square_match_reference(kind):
         assert list(o.shape) == g["observation_space"]["shape"]
         assert np.asarray(env.fov_loc).tolist() == g["fov_loc"] and bool(env.mask_out) == g["mask_out"]
         env.close()
+
+
+def test_dmc_reset_envs_after_episode_end_matches_oracle():
+    """DMCVecEnv with device outputs and autoreset=False: after an episode end the caller resets a subset with reset_envs().  The
+    reset envs give the oracle chain's reset observation, the others keep their previous observation bit for bit (in the fresh
+    output buffer), and stepping goes on in step with the oracle."""
+    from active_gym import DMCVecEnv
+    N, obs = 3, (32, 32)
+    fkw = dict(obs_size=obs, fov_size=(10, 12), fov_init_loc=(2, 3), sensory_action_mode="absolute")
+    args = _args(60, frame_stack=2, episode_len=9, mask_out=True, resize_to_full=False, device="cuda:0", **fkw)
+    env = DMCVecEnv(args, N, kind="fixed", autoreset=False)
+    recs = [O.RecordOracle(O.DMCEnvOracle(ScriptedDMC(60 + i, episode_len=9), obs_size=obs, frame_stack=2, action_repeat=4,
+                                          clip_reward=False, gray_mode="cv15")) for i in range(N)]
+    fovs = [O.FixedFovealOracle(resize_to_full=False, mask_out=True, **fkw) for _ in range(N)]
+    rng = np.random.default_rng(9)
+
+    def close(got, want):
+        np.testing.assert_allclose(got.cpu().numpy(), np.stack(want), rtol=0, atol=TOL)
+
+    def step():
+        motor = rng.uniform(-1, 1, (N, 2)).astype(np.float32)
+        sens = rng.uniform(-4, 30, (N, 2))
+        o, rew, term, trunc, infos = env.step({"motor_action": motor, "sensory_action": sens})
+        want = []
+        for i in range(N):
+            s, r, d, tr, info = recs[i].step(motor[i])
+            want.append(fovs[i].step(s.astype(np.float64), sens[i]))
+            assert float(rew[i]) == float(r) and bool(term[i]) == bool(d) and infos["ep_len"][i] == info["ep_len"]
+            assert np.array_equal(infos["fov_loc"][i].cpu().numpy(), fovs[i].fov_loc)
+        close(o, want)
+        assert "final_observation" not in infos                      # autoreset=False: nothing is reset inside step()
+        return o, term
+
+    def reset(idx, prev):
+        held = prev.clone()
+        o, infos = env.reset_envs(idx)
+        want = {i: fovs[i].reset(recs[i].reset()[0].astype(np.float64)) for i in idx}
+        for i in range(N):
+            if i in want:
+                np.testing.assert_allclose(o[i].cpu().numpy(), want[i], rtol=0, atol=TOL)
+                assert infos["ep_len"][i] == 0 and infos["reward"][i] == 0 and infos["discount"][i] is None
+                assert np.array_equal(infos["fov_loc"][i].cpu().numpy(), fovs[i].fov_loc)
+            else:
+                assert torch.equal(o[i], held[i])                    # not reset: the previous observation, bit for bit
+        assert torch.equal(prev, held)                               # ... and what the caller holds is not written
+        return o
+
+    o, _ = env.reset()
+    close(o, [fovs[i].reset(recs[i].reset()[0].astype(np.float64)) for i in range(N)])
+    term = np.zeros(N, bool)
+    while not term.any():
+        o, term = step()
+    assert term.all()                                                # the scripted episodes all end at t = 9
+    o = reset([0, 2], o)
+    o = reset([1], o)
+    for _ in range(2):
+        o, term = step()
+        assert not term.any()
+    env.close()

@@ -51,7 +51,7 @@ def one_case(k):
     env = AtariVecEnv(args, N, kind=kind, noop_fn=lambda: int(next(it_a)))
     if not on_device and rng.random() < 0.5:
         # host outputs through the recycled pinned pool whatever the batch size (the product uses it from 1 MB of observations up)
-        env._HOST_POOL_MIN_ELEMS = 0
+        env._host.min_elems = 0
         cfg["host_pool"] = True
     if not training:
         env.eval()

@@ -77,7 +77,7 @@ def chunks_probe(out, rounds, per_round, warm):
                 every[c] += ts
         # the emulators alone (the unchunked env's runner writes its own pinned staging), and this format's H2D bytes
         e0 = envs[0]
-        h2d_bytes = int(e0._h_frames.numel()) + N
+        h2d_bytes = int(e0._staging.h_frames.numel()) + N
         motor = np.zeros(N, np.int64)
         ts = []
         for _ in range(60):
