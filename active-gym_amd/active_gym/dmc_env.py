@@ -194,7 +194,10 @@ class DMCHostRunner:
 class DMCVecEnv(AtariVecEnv):
     """N DMC pixel envs of one kind on one GPU; same conventions as :class:`AtariVecEnv`, continuous motor
     actions ``(N, action_dim)`` in [-1, 1]; ``args.gray_mode`` = "cv15" (OpenCV 4.x, default) | "cv14" (gray only);
-    ``args.grey = False``: colour observations ``(N, fs, 3, H, W)``."""
+    ``args.grey = False``: colour observations ``(N, fs, 3, H, W)``.  ``args.step_log`` is refused: the step log's payload holds a
+    discrete motor action."""
+
+    _discrete_motor = False
 
     def _check_obs_size(self):
         if not getattr(self.args, "from_pixels", True):

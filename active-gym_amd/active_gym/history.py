@@ -59,6 +59,8 @@ def check_env_history(kind: str, history_len, channels: int = 1, ragged_obs: str
 
 
 class FrameHistory:
+    _steplogs = ()           # the steplog.StepLog objects on this history: clear() clears them too
+
     def __init__(self, pipe, capacity: int):
         """pipe: an ObsPipeline of kind "base" or "fixed" with gray frames; capacity: env-steps kept per env (>= frame_stack).
         Create it before the pipeline's first ingest (a new history takes the frames before an env's first append to be zero,
@@ -104,8 +106,11 @@ class FrameHistory:
         nat.check(rc, self.pipe._ctx)
 
     def clear(self):
-        """Every index becomes invalid, the per-env indices restart at 0."""
+        """Every index becomes invalid, the per-env indices restart at 0.  The step logs on this history are cleared with it (a
+        row recorded before the clear must not pass for one of a new index)."""
         self._check(self._lib.agx_history_clear(self._h, self.pipe._stream()))
+        for log in self._steplogs:
+            log.clear()
 
     def push(self, cmd: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """After one ingest(.., cmd) and its observation: append each env's newest frame and current fov_loc.  Returns the i64 [N]

@@ -76,7 +76,16 @@ class AtariVecEnv:
     ``history_len`` (T > 0, kinds base / fixed: the env owns a :class:`~active_gym.history.FrameHistory` of T env-steps per
     env as ``env.history``, pushes after every observation it returns - in the Python loop and in the native loop - and
     ``info["history_index"]`` is the index of the observation ``step`` / ``reset`` returned; for an env that was autoreset in
-    this step the terminal observation is ``index - 1``.  0, the default: no history, no key)."""
+    this step the terminal observation is ``index - 1``.  0, the default: no history, no key),
+    ``step_log`` (True, needs ``history_len`` > 0: the env owns a :class:`~active_gym.steplog.StepLog` on its history as
+    ``env.steplog`` and records after every ``step`` - in the Python loop and in the native loop - the step's returned reward,
+    flags = TERMINATED for ``done`` and the action as payload, at the index of the observation the step produced (the
+    terminal observation's for an env autoreset in this step).  The payload is the motor action as int32 (4 bytes, base env)
+    followed on a fixed env by the sensory action as two float32 (12 bytes): exact for integer-valued and float32 sensory
+    actions, a float64 one is rounded to float32.  It needs a discrete motor action (one integer per env): ``DMCVecEnv``, whose
+    motor actions are float vectors, refuses ``step_log`` in its constructor's first lines.  ``reset`` / ``reset_envs`` record
+    nothing.  ``env.replay_batch`` draws
+    learner batches from it.  False, the default: nothing new runs in ``step``)."""
 
     _loop = None             # NativeStepLoop when the native step loop drives this env (subclasses with their own source: never)
     _staging = None          # staging.Staging when the Python loop does
@@ -86,6 +95,11 @@ class AtariVecEnv:
     _host_step = None        # native_hostout.HostOutStep when host_obs_chunks > 0
     history = None           # history.FrameHistory when args.history_len > 0
     history_len = 0
+    steplog = None           # steplog.StepLog when args.step_log
+    step_log = False
+    _log_sets = None         # step_log: two (pinned, device, event) sets of the per-step upload, used alternately
+    _log_i = 0
+    _discrete_motor = True   # the motor action is one integer per env (what the step log's payload holds)
     _glimpse_of = None       # the history the cached glimpse.GlimpseMemory objects (by glimpses) read
     _replay_of = None        # the history the cached replay.ReplaySampler objects (by argument tuple) read
 
@@ -98,6 +112,8 @@ class AtariVecEnv:
         self.obs_dtype = _resolve_env_obs_dtype(args)
         from .history import check_env_history
         self.history_len = check_env_history(kind, getattr(args, "history_len", 0), 1, getattr(args, "ragged_obs", "padded"))
+        from .steplog import check_env_step_log
+        self.step_log = check_env_step_log(getattr(args, "step_log", False), self.history_len, self._discrete_motor)
         if not torch.cuda.is_available():
             raise RuntimeError("active_gym envs need a ROCm GPU: the observation pipeline has no CPU implementation")
         self.args = args
@@ -174,6 +190,17 @@ class AtariVecEnv:
         self._ragged_packed = kind == "flexible" and self._raw_crop and wants_packed(args)
         self.pipe = ObsPipeline(**kw)
         self.history = FrameHistory(self.pipe, self.history_len) if self.history_len > 0 else None
+        self.steplog = None
+        if self.step_log:
+            from .steplog import StepLog
+            self.steplog = StepLog(self.history, 12 if kind == "fixed" else 4)      # motor i32 [, sensory 2 x f32]
+            # (motor, reward bits, done) of a step travel in one pinned i32 [3, N] buffer; two sets, used alternately, each
+            # rewritten only after the event behind its last copy
+            n = self.num_envs
+            self._log_sets = [{"h": torch.empty((3, n), dtype=torch.int32, pin_memory=True),
+                               "d": torch.empty((3, n), dtype=torch.int32, device=self.device),
+                               "ev": torch.cuda.Event()} for _ in range(2)]
+            self._log_payload = torch.empty((n, 3), dtype=torch.int32, device=self.device) if kind == "fixed" else None
 
     def _build_spaces(self):
         kind = self.kind
@@ -381,11 +408,63 @@ class AtariVecEnv:
         """i64 [N]: the history index of each env's newest observation (NumPy with host outputs)."""
         return self._out(self.history.last_index())
 
+    def _log_step(self, motor, sens, reward, done):
+        """args.step_log: record what this step returned, after its pushes - one upload of (motor, reward, done), then device
+        work only.  Row = the newest index, or the one before it for an env that was autoreset in this step (its terminal
+        observation: the reset observation has no step behind it)."""
+        n = self.num_envs
+        st = self._log_sets[self._log_i]
+        self._log_i ^= 1
+        st["ev"].synchronize()                  # the copy that last read this pinned buffer, two steps ago
+        host = st["h"].numpy()
+        host[0] = np.asarray(motor).reshape(n)          # (the cast the runner itself makes)
+        host[1] = np.asarray(reward, dtype=np.float32).reshape(n).view(np.int32)
+        host[2] = np.asarray(done, dtype=bool).reshape(n)
+        d = st["d"]
+        d.copy_(st["h"], non_blocking=True)
+        st["ev"].record()
+        index = self.history.last_index()
+        if self.autoreset:
+            index -= d[2]
+        if sens is None:
+            payload = d[0].reshape(n, 1)
+        else:
+            payload = self._log_payload
+            payload[:, 0] = d[0]
+            payload[:, 1:] = sens.to(torch.float32).view(torch.int32)
+        self.steplog.record(index, d[1].view(torch.float32), d[2].to(torch.uint8), payload.view(torch.uint8))      # TERMINATED == 1
+
+    def replay_batch(self, B: int, nstep: int = 1, gamma: float = 0.99, glimpses: Optional[int] = None, **sampler_kw):
+        """B learner rows from the env's step log: ``steplog.batch(env.replay_sampler(**sampler_kw), B, nstep, gamma, glimpses)``
+        with the payload split into ``motor_action`` (i32 [B]) and, on a fixed env, ``sensory_action`` (f32 [B, 2]): the action
+        taken on seeing ``obs``.  ``ret`` / ``discount`` / ``next_obs`` are the n-step target's parts: target = ret + discount *
+        value(next_obs).  ``glimpses = P`` reads the observations through the glimpse memory (the sampler's ``back`` defaults to
+        P - 1 then).  Rows with ok = 0 are to be ignored.  Needs ``step_log``: ValueError otherwise."""
+        from .steplog import check_nstep
+        nstep = check_nstep(nstep)
+        if self.steplog is None:
+            raise ValueError("replay_batch needs a step log (AtariEnvArgs.step_log = True, history_len > 0)")
+        memory = None
+        if glimpses is not None:
+            sampler_kw.setdefault("back", int(glimpses) - 1)
+            memory = self._glimpse_mem(glimpses)                 # the env's own, shared with glimpse_memory()
+        out = self.steplog.batch(self.replay_sampler(**sampler_kw), B, nstep, gamma, glimpses, memory=memory)
+        words = out.pop("payload").view(torch.int32)
+        out["motor_action"] = words[:, 0].contiguous()
+        if self.kind == "fixed":
+            out["sensory_action"] = words[:, 1:3].contiguous().view(torch.float32)
+        return out
+
     def glimpse_memory(self, glimpses: int = 3, out: Optional[torch.Tensor] = None):
         """The glimpse memory of the observation the last ``reset`` / ``step`` returned, for all N envs: the elementwise
         maximum over each env's last up-to-``glimpses`` observations since its last reset (glimpse.GlimpseMemory.observe at
         ``history.last_index()``; an env autoreset in the last step gives just its returned observation).  Needs
         ``history_len`` > 0, kind "fixed" and mask_out or resize_to_full mode: ValueError otherwise."""
+        obs, _, _ = self._glimpse_mem(glimpses).observe(self._glimpse_env, self.history.last_index(), out=out)
+        return self._out(obs)
+
+    def _glimpse_mem(self, glimpses: int):
+        """The env's glimpse.GlimpseMemory of ``glimpses`` glimpses on its history, cached per value."""
         from .glimpse import GlimpseMemory
         if self.history is None:
             raise ValueError("glimpse_memory needs a frame history (AtariEnvArgs.history_len > 0)")
@@ -395,8 +474,7 @@ class AtariVecEnv:
         mem = self._glimpse.get(int(glimpses))
         if mem is None:
             mem = self._glimpse[int(glimpses)] = GlimpseMemory(self.history, glimpses)      # ValueError for a kind or mode that is not served
-        obs, _, _ = mem.observe(self._glimpse_env, self.history.last_index(), out=out)
-        return self._out(obs)
+        return mem
 
     def replay_sampler(self, back: int = 0, forward: int = 1, attempts: int = 16, seed: Optional[int] = None):
         """A replay.ReplaySampler on the env's frame history, cached per argument tuple: ``sample(B)`` draws (env, index) pairs
@@ -552,6 +630,8 @@ class AtariVecEnv:
                 else:
                     infos[key] = np.where(done.reshape((n,) + (1,) * (info[key].ndim - 1)), rinfo[key], info[key])
             attach_final(infos, done, *final)
+        if self.steplog is not None:
+            self._log_step(motor, sens, reward, done)
         st.release()
         return self._ret_obs(obs), reward, done, truncated, infos
 
@@ -601,6 +681,8 @@ class AtariVecEnv:
         infos = with_masks(info, n)
         if final is not None:
             attach_final(infos, done, *final)
+        if self.steplog is not None:
+            self._log_step(motor, sens, reward, done)
         obs = self._host.hand_out(h) if h is not None else self._ret_obs(self._obs)
         return obs, reward, done, truncated, infos
 
