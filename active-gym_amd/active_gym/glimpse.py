@@ -2,7 +2,7 @@
 persistence-of-vision memory), written by one kernel from the frame history's u8 frames and recorded fov_loc.
 
     hist = FrameHistory(pipe, capacity=100_000)
-    mem = GlimpseMemory(hist, glimpses=3)
+    mem = hist.memory(3)                            # the history's one memory of 3 glimpses
     ...
     obs, loc, taken = mem.observe(env, index)       # max over the last up-to-3 observations of the sample's episode
 
@@ -65,21 +65,10 @@ class GlimpseMemory:
 def observe_memory(history, glimpses: int, env, index, out=None, loc_out=None, taken_out=None):
     """agx_history_observe_memory on a FrameHistory (no Python-side refusals: the library's own codes come back as AgxError)."""
     pipe = history.pipe
-    if not isinstance(env, torch.Tensor) or env.dim() != 1:
-        raise ValueError("env must be a 1-D int32 tensor")
-    b, p = int(env.shape[0]), int(glimpses)
-    pe = pipe._chk(env, (b,), torch.int32, "env")
-    pi = pipe._chk(index, (b,), torch.int64, "index")
-    shape = (b,) + history.obs_row_shape()
-    if out is None:
-        out = torch.empty(shape, dtype=pipe.obs_dtype, device=history.device)
-    po = pipe._chk(out, shape, pipe.obs_dtype, "out")
-    lshape = (b, max(p, 0), 2)
-    if loc_out is None:
-        loc_out = torch.empty(lshape, dtype=torch.int32, device=history.device)
-    pl = pipe._chk(loc_out, lshape, torch.int32, "loc_out")
-    if taken_out is None:
-        taken_out = torch.empty((b,), dtype=torch.uint8, device=history.device)
-    pt = pipe._chk(taken_out, (b,), torch.uint8, "taken_out")
+    b, pe, pi = pipe._pair(env, index)
+    p = int(glimpses)
+    out, po = pipe._out(out, (b,) + history.obs_row_shape(), pipe.obs_dtype, "out")
+    loc_out, pl = pipe._out(loc_out, (b, max(p, 0), 2), torch.int32, "loc_out")
+    taken_out, pt = pipe._out(taken_out, (b,), torch.uint8, "taken_out")
     nat.check(lib().agx_history_observe_memory(history.handle, p, pe, pi, b, po, pl, pt, pipe._stream()), pipe._ctx)
     return out, loc_out, taken_out

@@ -21,6 +21,7 @@ from typing import Optional
 import torch
 
 from . import _native as nat
+from .lifetime import Owner
 
 _P = C.c_void_p
 HIST_FOVEA, HIST_FULL = 0, 1          # AGX_HIST_*
@@ -58,9 +59,7 @@ def check_env_history(kind: str, history_len, channels: int = 1, ragged_obs: str
     return t
 
 
-class FrameHistory:
-    _steplogs = ()           # the steplog.StepLog objects on this history: clear() clears them too
-
+class FrameHistory(Owner):
     def __init__(self, pipe, capacity: int):
         """pipe: an ObsPipeline of kind "base" or "fixed" with gray frames; capacity: env-steps kept per env (>= frame_stack).
         Create it before the pipeline's first ingest (a new history takes the frames before an env's first append to be zero,
@@ -72,23 +71,10 @@ class FrameHistory:
         self.num_envs = pipe.num_envs
         self._h = _P()
         nat.check(self._lib.agx_history_create(pipe._ctx, self.capacity, C.byref(self._h)), pipe._ctx)
-        # the history holds the context's raw handle: it goes before the pipeline does
-        if not hasattr(pipe, "_dependents"):
-            pipe._dependents = []
-        pipe._dependents.append(self)
-
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h.value:
-            self._lib.agx_history_destroy(self._h)
-            self._h = _P()
-            if self in getattr(self.pipe, "_dependents", ()):
-                self.pipe._dependents.remove(self)
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:  # noqa: BLE001
-            pass
+        # the history holds the context's raw handle: it goes before the pipeline does; the samplers and step logs on it are
+        # its children and go before it
+        self._own(self._h, self._lib.agx_history_destroy, (pipe,))
+        self._memories, self._samplers = {}, {}
 
     @property
     def handle(self):
@@ -109,26 +95,22 @@ class FrameHistory:
         """Every index becomes invalid, the per-env indices restart at 0.  The step logs on this history are cleared with it (a
         row recorded before the clear must not pass for one of a new index)."""
         self._check(self._lib.agx_history_clear(self._h, self.pipe._stream()))
-        for log in self._steplogs:
-            log.clear()
+        from .steplog import StepLog
+        for child in self._children:
+            if isinstance(child, StepLog):          # (a sampler keeps no rows)
+                child.clear()
 
     def push(self, cmd: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """After one ingest(.., cmd) and its observation: append each env's newest frame and current fov_loc.  Returns the i64 [N]
         index of the append (-1 for an env whose command byte carries CMD_SKIP).  One push per ingest."""
-        n = self.num_envs
-        pc = self._chk(cmd, (n,), torch.uint8, "cmd")
-        if out is None:
-            out = torch.empty((n,), dtype=torch.int64, device=self.device)
-        po = self._chk(out, (n,), torch.int64, "out")
+        pc = self._chk(cmd, (self.num_envs,), torch.uint8, "cmd")
+        out, po = self.pipe._out(out, (self.num_envs,), torch.int64, "out")
         self._check(self._lib.agx_history_push(self._h, pc, po, self.pipe._stream()))
         return out
 
     def last_index(self, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """i64 [N]: the index of each env's newest append (-1: none yet)."""
-        n = self.num_envs
-        if out is None:
-            out = torch.empty((n,), dtype=torch.int64, device=self.device)
-        po = self._chk(out, (n,), torch.int64, "out")
+        out, po = self.pipe._out(out, (self.num_envs,), torch.int64, "out")
         self._check(self._lib.agx_history_last_index(self._h, po, self.pipe._stream()))
         return out
 
@@ -143,33 +125,47 @@ class FrameHistory:
         sensory action to look at instead.  what: "fovea" (the pipeline's own observation) or "full" (the stack, k/255).
         Returns (obs [B, ...], fov_loc i32 [B, 2], valid u8 [B]); rows of invalid samples (never issued, or evicted) are left as
         they were in `out` / `loc_out` (uninitialised when this call allocated them).  fov_loc is not written by a base pipeline."""
-        from .pipeline import _DT
         if what not in _WHAT:
             raise ValueError(f"what must be 'fovea' or 'full', got {what!r}")
-        if not isinstance(env, torch.Tensor) or env.dim() != 1:
-            raise ValueError("env must be a 1-D int32 tensor")
-        b = int(env.shape[0])
-        pe = self._chk(env, (b,), torch.int32, "env")
-        pi = self._chk(index, (b,), torch.int64, "index")
-        pa, dt = None, 0
-        if action is not None:
-            if action.dtype not in _DT:
-                raise TypeError(f"sensory action dtype {action.dtype} not supported (f32/f64/i32/i64)")
-            pa = self._chk(action, (b, 2), None, "action")
-            dt = _DT[action.dtype]
-        shape = (b,) + self.obs_row_shape(what)
-        if out is None:
-            out = torch.empty(shape, dtype=self.pipe.obs_dtype, device=self.device)
-        po = self._chk(out, shape, self.pipe.obs_dtype, "out")
-        if loc_out is None:
-            loc_out = torch.empty((b, 2), dtype=torch.int32, device=self.device)
-        pl = self._chk(loc_out, (b, 2), torch.int32, "loc_out")
-        if valid_out is None:
-            valid_out = torch.empty((b,), dtype=torch.uint8, device=self.device)
-        pv = self._chk(valid_out, (b,), torch.uint8, "valid_out")
+        pipe = self.pipe
+        b, pe, pi = pipe._pair(env, index)
+        pa, dt = pipe._action(action, b)
+        out, po = pipe._out(out, (b,) + self.obs_row_shape(what), pipe.obs_dtype, "out")
+        loc_out, pl = pipe._out(loc_out, (b, 2), torch.int32, "loc_out")
+        valid_out, pv = pipe._out(valid_out, (b,), torch.uint8, "valid_out")
         self._check(self._lib.agx_history_observe(self._h, _WHAT[what], pe, pi, b, pa, dt, po, pl, pv, self.pipe._stream()))
         return out, loc_out, valid_out
 
     def attach(self, loop):
         """The native step loop pushes from now on (agx_loop_set_history); ``loop``: a NativeStepLoop of the same pipeline."""
         loop.check(self._lib.agx_loop_set_history(loop.handle, self._h))
+        # the loop pushes through the raw handle: a history that closes under a live loop takes itself out of it first
+        self._while_both_alive(loop, lambda: self._lib.agx_loop_set_history(loop.handle, None))
+
+    def memory(self, glimpses: int):
+        """The one glimpse.GlimpseMemory of ``glimpses`` glimpses on this history, made at first use (ValueError for a kind or
+        mode that is not served): what ReplaySampler.transitions, StepLog.batch and the env's glimpse_memory read through."""
+        mem = self._memories.get(int(glimpses))
+        if mem is None:
+            from .glimpse import GlimpseMemory
+            mem = self._memories[int(glimpses)] = GlimpseMemory(self, glimpses)
+        return mem
+
+    def sampler(self, back: int = 0, forward: int = 1, attempts: int = 16, seed: int = 0):
+        """The one replay.ReplaySampler of this argument tuple on this history, made at first use."""
+        key = (int(back), int(forward), int(attempts), int(seed))
+        smp = self._samplers.get(key)
+        if smp is None:
+            from .replay import ReplaySampler
+            smp = self._samplers[key] = ReplaySampler(self, back, forward, attempts, seed)
+        return smp
+
+    def transition_obs(self, read, env, index, next_index) -> dict:
+        """The observation part of a transition batch through ``read`` (``self.observe`` or a GlimpseMemory's): obs, next_obs
+        and, on a fixed pipeline, fov_loc, next_fov_loc."""
+        obs, loc, _ = read(env, index)
+        nobs, nloc, _ = read(env, next_index)
+        out = {"obs": obs, "next_obs": nobs}
+        if self.pipe.kind == "fixed":
+            out["fov_loc"], out["next_fov_loc"] = loc, nloc
+        return out

@@ -15,6 +15,7 @@ import numpy as np
 import torch
 
 from . import _native as nat
+from .lifetime import Owner
 
 _P = C.c_void_p
 STEP_FN = C.CFUNCTYPE(C.c_int, _P, _P, _P, _P, _P, _P, _P)
@@ -61,7 +62,7 @@ def _view(ptr, shape, typestr, device):
     return torch.as_tensor(_DeviceView(ptr, shape, typestr), device=device)
 
 
-class NativeStepLoop:
+class NativeStepLoop(Owner):
     def __init__(self, pipe, runner, gray: bool, compact: bool, autoreset: bool):
         """pipe: ObsPipeline; runner: NativeHostRunner (its libagx_runner.so handle and entry points become the host source)."""
         self._lib = _lib()
@@ -80,10 +81,7 @@ class NativeStepLoop:
         if rc:
             raise nat.AgxError(rc, (self._lib.agx_loop_last_error(None) or b"").decode())
         # the loop holds the raw handles of both: whichever of the three is closed (or finalized) first closes the loop first
-        for owner in (pipe, runner):
-            if not hasattr(owner, "_dependents"):
-                owner._dependents = []
-            owner._dependents.append(self)
+        self._own(self._h, self._destroy_loop, (pipe, runner))
         self.n = pipe.num_envs
         self._motor = np.zeros(self.n, np.int32)
         self._motor_ptr = self._motor.ctypes.data
@@ -91,20 +89,9 @@ class NativeStepLoop:
         self._res = AgxLoopResult()
         self._cb_error = None
 
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h.value:
-            self._views = {}                                       # views of buffers that are about to be freed
-            self._lib.agx_loop_destroy(self._h)
-            self._h = _P()
-            for owner in (self.pipe, self.runner):
-                if self in getattr(owner, "_dependents", ()):
-                    owner._dependents.remove(self)
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:  # noqa: BLE001
-            pass
+    def _destroy_loop(self, h):
+        self._views = {}                                           # views of buffers that are about to be freed
+        self._lib.agx_loop_destroy(h)
 
     def _check(self, rc):
         if self._cb_error is not None:

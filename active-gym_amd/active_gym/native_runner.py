@@ -13,6 +13,7 @@ import numpy as np
 
 from . import _native as nat
 from .frame_source import RAW_H, RAW_W, resolve_frame_format
+from .lifetime import Owner
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("AGXR_LIB") or os.path.join(os.path.dirname(_HERE), "lib", "libagx_runner.so")     # AGXR_LIB: a sanitizer build (tools/README.md)
@@ -72,7 +73,7 @@ def _find_libale_c():
     raise ImportError("libale_c.so not found inside atari_py")
 
 
-class NativeHostRunner:
+class NativeHostRunner(Owner):
     def __init__(self, args, num_envs: int, frames: Optional[np.ndarray] = None, workers: Optional[int] = None,
                  noop_fn: Optional[Callable[[], int]] = None, env_offset: int = 0, backend: str = "scripted",
                  noop_per_env: bool = False, src_rows: Optional[Sequence[int]] = None, cpus: Optional[Sequence[int]] = None,
@@ -118,6 +119,7 @@ class NativeHostRunner:
         rc = self._lib.agxr_create(C.byref(cfg), C.byref(self._h))
         if rc:
             raise RuntimeError("agxr_create: " + (self._lib.agxr_last_error(None) or b"").decode())
+        self._own(self._h, self._lib.agxr_destroy)         # (a native step loop holds this raw handle as its host source: it goes first)
         self.num_actions = self._lib.agxr_num_actions(self._h)
         self.actions = [list(range(self.num_actions))] * self.num_envs
         self.num_workers = self._lib.agxr_num_threads(self._h)
@@ -140,19 +142,6 @@ class NativeHostRunner:
     def _check(self, rc):
         if rc:
             raise RuntimeError("libagx_runner: " + (self._lib.agxr_last_error(self._h) or b"").decode())
-
-    def close(self):
-        for dep in list(getattr(self, "_dependents", ())):      # a native step loop holds this runner's raw handle as its host source
-            dep.close()
-        if getattr(self, "_h", None) is not None and self._h.value:
-            self._lib.agxr_destroy(self._h)
-            self._h = _P()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:  # noqa: BLE001
-            pass
 
     def set_frames(self, frames: np.ndarray):
         """Point the runner at another staging buffer of the same shape (double-buffered pinned staging)."""

@@ -17,6 +17,7 @@ import numpy as np
 import torch
 
 from . import _native as nat
+from .lifetime import Owner
 
 _KINDS = {"base": nat.KIND_BASE, "fixed": nat.KIND_FIXED, "flexible": nat.KIND_FLEXIBLE,
           "peripheral": nat.KIND_PERIPHERAL}
@@ -24,6 +25,15 @@ _DT = {torch.float32: nat.DT_F32, torch.float64: nat.DT_F64, torch.int32: nat.DT
 # observation element types: name -> (torch dtype, agx_config.out_mode bits)
 OBS_DTYPES = {"float32": (torch.float32, nat.OBS_F32), "bfloat16": (torch.bfloat16, nat.OBS_BF16),
               "float16": (torch.float16, nat.OBS_F16)}
+
+
+def action_dt(action) -> int:
+    """The AGX_DT_* of a sensory action tensor (0 for None); TypeError for an element type the kernels do not read."""
+    if action is None:
+        return 0
+    if action.dtype not in _DT:
+        raise TypeError(f"sensory action dtype {action.dtype} not supported (f32/f64/i32/i64)")
+    return _DT[action.dtype]
 
 
 def resolve_obs_dtype(obs_dtype) -> torch.dtype:
@@ -49,7 +59,9 @@ def resolve_out_mode(mask_out: bool, resize_to_full: bool) -> int:
     return nat.OUT_RAW
 
 
-class ObsPipeline:
+class ObsPipeline(Owner):
+    _n_src = None            # rows of a compact screen (_compact_rows)
+
     def __init__(self, num_envs: int, kind: str = "fixed", obs_size: Tuple[int, int] = (84, 84),
                  frame_stack: int = 4, fov_size: Optional[Tuple[int, int]] = None,
                  fov_init_loc: Sequence[float] = (0, 0), sensory_action_mode: str = "absolute",
@@ -120,6 +132,8 @@ class ObsPipeline:
         self._cfg = cfg
         self._ctx = C.c_void_p()
         nat.check(self._lib.agx_create(C.byref(cfg), C.byref(self._ctx)))
+        # a history or a native step loop built on this context holds the raw handle: they go first (lifetime.py)
+        self._own(self._ctx, self._lib.agx_destroy)
         dims = (C.c_int32 * 4)()
         nat.check(self._lib.agx_obs_shape(self._ctx, C.byref(dims)), self._ctx)
         # the ABI reports {N, 3 fs, h, w} for colour: the same bytes as [N][fs][3][h][w]
@@ -128,21 +142,6 @@ class ObsPipeline:
         self.full_shape = (self.num_envs,) + chan + self.obs_size
 
     # ------------------------------------------------------------------ plumbing
-    def close(self):
-        # a native step loop built on this context holds the raw handle: it goes first (also when the garbage collector runs the
-        # finalizers of an abandoned env in an order of its own)
-        for dep in list(getattr(self, "_dependents", ())):
-            dep.close()
-        if getattr(self, "_ctx", None) is not None and self._ctx.value:
-            self._lib.agx_destroy(self._ctx)
-            self._ctx = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
     def _stream(self):
         return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
 
@@ -158,6 +157,48 @@ class ObsPipeline:
         if not t.is_contiguous():
             raise ValueError(f"{name} must be contiguous")
         return C.c_void_p(t.data_ptr())
+
+    # The one place that marshals arguments, for this class and for the bindings on it (history, glimpse, replay, steplog).
+    # None of these synchronises, or allocates beyond the output the caller left out: they run inside captured graphs.
+    def _out(self, t: Optional[torch.Tensor], shape, dtype, name):
+        """An output the caller passed, checked, or a new uninitialised one (right by construction) -> (tensor, pointer)."""
+        if t is None:
+            t = torch.empty(shape, dtype=dtype, device=self.device)
+            return t, C.c_void_p(t.data_ptr())
+        return t, self._chk(t, shape, dtype, name)
+
+    def _action(self, action: Optional[torch.Tensor], rows: int):
+        """A sensory action [rows, 2] or None -> (pointer | None, AGX_DT_*)."""
+        dt = action_dt(action)
+        return (None if action is None else self._chk(action, (rows, 2), None, "action")), dt
+
+    def _pair(self, env, index):
+        """The samples (env i32 [B], index i64 [B]) of the history's readers -> (B, env pointer, index pointer)."""
+        if not isinstance(env, torch.Tensor) or env.dim() != 1:
+            raise ValueError("env must be a 1-D int32 tensor")
+        b = int(env.shape[0])
+        return b, self._chk(env, (b,), torch.int32, "env"), self._chk(index, (b,), torch.int64, "index")
+
+    def _compact_rows(self) -> int:
+        """len(source_rows()), looked up once."""
+        if self._n_src is None:
+            self._n_src = len(self.source_rows())
+        return self._n_src
+
+    def _packed_outputs(self, action, action_type, packed, offsets, loc_out, res_out):
+        """What fovea_packed and step_flexible_packed share: the action and the four packed outputs, allocated where left out
+        -> (the tensors to return, the ABI's arguments from the action to the fov_res)."""
+        N = self.num_envs
+        pa, dt = self._action(action, N)
+        pt = self._chk(action_type, (N,), torch.int32, "action_type") if action_type is not None else None
+        if packed is None:
+            packed = torch.empty((N * self.frame_stack * self.obs_size[0] * self.obs_size[1],), dtype=torch.float32, device=self.device)
+        if packed.dtype != torch.float32 or packed.device != self.device or packed.dim() != 1 or not packed.is_contiguous():
+            raise ValueError("packed must be a contiguous 1-D float32 tensor on the pipeline's device")
+        offsets, pof = self._out(offsets, (N + 1,), torch.int64, "offsets")
+        loc_out, pl = self._out(loc_out, (N, 2), torch.int32, "loc_out")
+        res_out, pr = self._out(res_out, (N, 2), torch.int32, "res_out")
+        return (packed, offsets, loc_out, res_out), (pa, dt, pt, C.c_void_p(packed.data_ptr()), packed.numel(), pof, pl, pr)
 
     def algorithmic_bytes(self, kernel: str) -> int:
         k = {"ingest": nat.K_INGEST, "fovea": nat.K_FOVEA, "full": nat.K_FULL, "ingest_rgb": nat.K_INGEST_RGB,
@@ -204,16 +245,14 @@ class ObsPipeline:
 
     def ingest_compact(self, rows: torch.Tensor, cmd: torch.Tensor):
         """:meth:`ingest` from compact screens u8[N,2,n_rows,160,3]: row k = screen row ``source_rows()[k]``; same results."""
-        n = len(self.source_rows()) if not hasattr(self, "_n_src") else self._n_src
-        self._n_src = n
+        n = self._compact_rows()
         pf = self._chk(rows, (self.num_envs, 2, n, nat.RAW_W, 3), torch.uint8, "rows")
         pc = self._chk(cmd, (self.num_envs,), torch.uint8, "cmd")
         nat.check(self._lib.agx_ingest_compact(self._ctx, pf, pc, self._stream()), self._ctx)
 
     def ingest_gray_raw_compact(self, rows: torch.Tensor, cmd: torch.Tensor):
         """:meth:`ingest_gray_raw` from compact grayscale screens u8[N,2,n_rows,160]."""
-        n = len(self.source_rows()) if not hasattr(self, "_n_src") else self._n_src
-        self._n_src = n
+        n = self._compact_rows()
         pg = self._chk(rows, (self.num_envs, 2, n, nat.RAW_W), torch.uint8, "rows")
         pc = self._chk(cmd, (self.num_envs,), torch.uint8, "cmd")
         nat.check(self._lib.agx_ingest_gray_raw_compact(self._ctx, pg, pc, self._stream()), self._ctx)
@@ -236,18 +275,9 @@ class ObsPipeline:
         N = self.num_envs
         pf = self._chk(frames, (N, 2, nat.RAW_H, nat.RAW_W, 3), torch.uint8, "frames")
         pc = self._chk(cmd, (N,), torch.uint8, "cmd")
-        pa, dt = None, 0
-        if action is not None:
-            if action.dtype not in _DT:
-                raise TypeError(f"sensory action dtype {action.dtype} not supported (f32/f64/i32/i64)")
-            pa = self._chk(action, (N, 2), None, "action")
-            dt = _DT[action.dtype]
-        if out is None:
-            out = torch.empty(self.obs_shape, dtype=self.obs_dtype, device=self.device)
-        po = self._chk(out, self.obs_shape, self.obs_dtype, "out")
-        if loc_out is None:
-            loc_out = torch.empty((N, 2), dtype=torch.int32, device=self.device)
-        pl = self._chk(loc_out, (N, 2), torch.int32, "loc_out")
+        pa, dt = self._action(action, N)
+        out, po = self._out(out, self.obs_shape, self.obs_dtype, "out")
+        loc_out, pl = self._out(loc_out, (N, 2), torch.int32, "loc_out")
         pe = C.c_void_p(mid_event.cuda_event) if mid_event is not None else None
         nat.check(self._lib.agx_step_fixed(self._ctx, pf, pc, pa, dt, po, pl, pe, self._stream()), self._ctx)
         return out, loc_out
@@ -264,9 +294,7 @@ class ObsPipeline:
         nat.check(self._lib.agx_ingest_rgb(self._ctx, pf, pc, int(gray_mode), self._stream()), self._ctx)
 
     def observe_full(self, out: Optional[torch.Tensor] = None) -> torch.Tensor:
-        if out is None:
-            out = torch.empty(self.full_shape, dtype=self.obs_dtype, device=self.device)
-        po = self._chk(out, self.full_shape, self.obs_dtype, "out")
+        out, po = self._out(out, self.full_shape, self.obs_dtype, "out")
         nat.check(self._lib.agx_observe_full(self._ctx, po, self._stream()), self._ctx)
         return out
 
@@ -288,30 +316,9 @@ class ObsPipeline:
         ``packed[offsets[n]:offsets[n+1]].view(fs, rh, rw)``."""
         if self.kind != "flexible" or self.out_mode != nat.OUT_RAW:
             raise RuntimeError("fovea_packed needs kind='flexible' in raw-crop mode (no mask_out, no resize_to_full)")
-        N = self.num_envs
-        pa, dt = None, 0
-        if action is not None:
-            if action.dtype not in _DT:
-                raise TypeError(f"sensory action dtype {action.dtype} not supported (f32/f64/i32/i64)")
-            pa = self._chk(action, (N, 2), None, "action")
-            dt = _DT[action.dtype]
-        pt = self._chk(action_type, (N,), torch.int32, "action_type") if action_type is not None else None
-        if packed is None:
-            packed = torch.empty((N * self.frame_stack * self.obs_size[0] * self.obs_size[1],), dtype=torch.float32, device=self.device)
-        if packed.dtype != torch.float32 or packed.device != self.device or packed.dim() != 1 or not packed.is_contiguous():
-            raise ValueError("packed must be a contiguous 1-D float32 tensor on the pipeline's device")
-        if offsets is None:
-            offsets = torch.empty((N + 1,), dtype=torch.int64, device=self.device)
-        pof = self._chk(offsets, (N + 1,), torch.int64, "offsets")
-        if loc_out is None:
-            loc_out = torch.empty((N, 2), dtype=torch.int32, device=self.device)
-        if res_out is None:
-            res_out = torch.empty((N, 2), dtype=torch.int32, device=self.device)
-        pl = self._chk(loc_out, (N, 2), torch.int32, "loc_out")
-        pr = self._chk(res_out, (N, 2), torch.int32, "res_out")
-        nat.check(self._lib.agx_fovea_flexible_packed(self._ctx, pa, dt, pt, C.c_void_p(packed.data_ptr()), packed.numel(), pof, pl,
-                                                      pr, self._stream()), self._ctx)
-        return packed, offsets, loc_out, res_out
+        outs, args = self._packed_outputs(action, action_type, packed, offsets, loc_out, res_out)
+        nat.check(self._lib.agx_fovea_flexible_packed(self._ctx, *args, self._stream()), self._ctx)
+        return outs
 
     def step_flexible_packed(self, screens: torch.Tensor, cmd: torch.Tensor, action: Optional[torch.Tensor] = None,
                              action_type: Optional[torch.Tensor] = None, packed: Optional[torch.Tensor] = None,
@@ -324,41 +331,20 @@ class ObsPipeline:
         if self.kind != "flexible" or self.out_mode != nat.OUT_RAW:
             raise RuntimeError("step_flexible_packed needs kind='flexible' in raw-crop mode (no mask_out, no resize_to_full)")
         N = self.num_envs
-        if not hasattr(self, "_n_src"):
-            self._n_src = len(self.source_rows())
+        n_src = self._compact_rows()
         if not isinstance(screens, torch.Tensor) or screens.dim() not in (4, 5):
             raise ValueError("screens must be a u8 tensor [N,2,rows,160,3] (RGB) or [N,2,rows,160] (gray)")
         gray = screens.dim() == 4
         rows = int(screens.shape[2])
-        if rows not in (nat.RAW_H, self._n_src):
-            raise ValueError(f"screens have {rows} rows; whole screens have {nat.RAW_H}, compact ones {self._n_src}")
+        if rows not in (nat.RAW_H, n_src):
+            raise ValueError(f"screens have {rows} rows; whole screens have {nat.RAW_H}, compact ones {n_src}")
         compact = rows != nat.RAW_H
         ps = self._chk(screens, (N, 2, rows, nat.RAW_W) + (() if gray else (3,)), torch.uint8, "screens")
         pc = self._chk(cmd, (N,), torch.uint8, "cmd")
-        pa, dt = None, 0
-        if action is not None:
-            if action.dtype not in _DT:
-                raise TypeError(f"sensory action dtype {action.dtype} not supported (f32/f64/i32/i64)")
-            pa = self._chk(action, (N, 2), None, "action")
-            dt = _DT[action.dtype]
-        pt = self._chk(action_type, (N,), torch.int32, "action_type") if action_type is not None else None
-        if packed is None:
-            packed = torch.empty((N * self.frame_stack * self.obs_size[0] * self.obs_size[1],), dtype=torch.float32, device=self.device)
-        if packed.dtype != torch.float32 or packed.device != self.device or packed.dim() != 1 or not packed.is_contiguous():
-            raise ValueError("packed must be a contiguous 1-D float32 tensor on the pipeline's device")
-        if offsets is None:
-            offsets = torch.empty((N + 1,), dtype=torch.int64, device=self.device)
-        pof = self._chk(offsets, (N + 1,), torch.int64, "offsets")
-        if loc_out is None:
-            loc_out = torch.empty((N, 2), dtype=torch.int32, device=self.device)
-        if res_out is None:
-            res_out = torch.empty((N, 2), dtype=torch.int32, device=self.device)
-        pl = self._chk(loc_out, (N, 2), torch.int32, "loc_out")
-        pr = self._chk(res_out, (N, 2), torch.int32, "res_out")
+        outs, args = self._packed_outputs(action, action_type, packed, offsets, loc_out, res_out)
         layout = (nat.SCREENS_GRAY if gray else 0) | (nat.SCREENS_COMPACT if compact else 0)
-        nat.check(self._lib.agx_step_flexible_packed(self._ctx, ps, layout, pc, pa, dt, pt, C.c_void_p(packed.data_ptr()), packed.numel(),
-                                                     pof, pl, pr, self._stream()), self._ctx)
-        return packed, offsets, loc_out, res_out
+        nat.check(self._lib.agx_step_flexible_packed(self._ctx, ps, layout, pc, *args, self._stream()), self._ctx)
+        return outs
 
     def fovea_reset(self, mask: Optional[torch.Tensor] = None):
         pm = self._chk(mask, (self.num_envs,), torch.uint8, "mask") if mask is not None else None
@@ -384,19 +370,10 @@ class ObsPipeline:
         if self.kind == "base":
             raise RuntimeError("base pipeline has no fovea; use observe_full()")
         N = self.num_envs
-        pa, dt = None, 0
-        if action is not None:
-            if action.dtype not in _DT:
-                raise TypeError(f"sensory action dtype {action.dtype} not supported (f32/f64/i32/i64)")
-            pa = self._chk(action, (N, 2), None, "action")
-            dt = _DT[action.dtype]
+        pa, dt = self._action(action, N)
         pm = self._chk(mask, (N,), torch.uint8, "mask") if mask is not None else None
-        if out is None:
-            out = torch.empty(self.obs_shape, dtype=self.obs_dtype, device=self.device)
-        po = self._chk(out, self.obs_shape, self.obs_dtype, "out")
-        if loc_out is None:
-            loc_out = torch.empty((N, 2), dtype=torch.int32, device=self.device)
-        pl = self._chk(loc_out, (N, 2), torch.int32, "loc_out")
+        out, po = self._out(out, self.obs_shape, self.obs_dtype, "out")
+        loc_out, pl = self._out(loc_out, (N, 2), torch.int32, "loc_out")
         st = self._stream()
         if self.kind == "fixed":
             nat.check(self._lib.agx_fovea_fixed(self._ctx, pa, dt, pm, po, pl, st), self._ctx)
@@ -405,8 +382,6 @@ class ObsPipeline:
             nat.check(self._lib.agx_fovea_peripheral(self._ctx, pa, dt, pm, po, pl, st), self._ctx)
             return out, loc_out
         pt = self._chk(action_type, (N,), torch.int32, "action_type") if action_type is not None else None
-        if res_out is None:
-            res_out = torch.empty((N, 2), dtype=torch.int32, device=self.device)
-        pr = self._chk(res_out, (N, 2), torch.int32, "res_out")
+        res_out, pr = self._out(res_out, (N, 2), torch.int32, "res_out")
         nat.check(self._lib.agx_fovea_flexible(self._ctx, pa, dt, pt, pm, po, pl, pr, st), self._ctx)
         return out, loc_out, res_out

@@ -25,6 +25,7 @@ from typing import Optional
 import torch
 
 from . import _native as nat
+from .lifetime import Owner
 
 _P = C.c_void_p
 SPAN_LIMIT = 64                       # AGX_REPLAY_SPAN_LIMIT
@@ -63,7 +64,9 @@ def check_transitions(back: int, forward: int, glimpses) -> None:
         raise ValueError(f"glimpses = {glimpses} needs a sampler with back >= {int(glimpses) - 1} (so that every memory is full), got back = {back}")
 
 
-class ReplaySampler:
+class ReplaySampler(Owner):
+    _closed_what = "the sampler or its history"
+
     def __init__(self, history, back: int = 0, forward: int = 1, attempts: int = 16, seed: int = 0):
         """history: a FrameHistory; back: earlier appends of the episode that must be valid too (a glimpse memory of back + 1
         glimpses is then full); forward: later appends of the same episode that must exist (1: transitions); attempts: draws
@@ -74,31 +77,12 @@ class ReplaySampler:
         self.pipe = history.pipe
         self.device = history.device
         self._r = _P()
-        self._mem = {}
         nat.check(self._lib.agx_replay_create(history.handle, self.back, self.forward, self.attempts, C.byref(self._r)), self.pipe._ctx)
-        # the sampler holds the history's raw handle: it goes before the history does (the pipeline closes its dependents in order)
-        deps = self.pipe._dependents
-        deps.insert(deps.index(history) if history in deps else 0, self)
+        # the sampler holds the history's raw handle: it goes before the history does
+        self._own(self._r, self._lib.agx_replay_destroy, (history,))
         self._total = torch.zeros((1,), dtype=torch.int64, device=self.device)
         if int(seed):
             self.seed(seed)
-
-    def close(self):
-        if getattr(self, "_r", None) is not None and self._r.value:
-            self._lib.agx_replay_destroy(self._r)
-            self._r = _P()
-            if self in getattr(self.pipe, "_dependents", ()):
-                self.pipe._dependents.remove(self)
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:  # noqa: BLE001
-            pass
-
-    def _live(self):
-        if not self._r.value or not self.history.handle.value:
-            raise RuntimeError("the sampler or its history is closed")
 
     def _check(self, rc):
         nat.check(rc, self.pipe._ctx)
@@ -116,14 +100,10 @@ class ReplaySampler:
         B = int(B)
         if B < 0:
             raise ValueError(f"B must be >= 0, got {B}")
-        chk = self.pipe._chk
-        if env_out is None:
-            env_out = torch.empty((B,), dtype=torch.int32, device=self.device)
-        if index_out is None:
-            index_out = torch.empty((B,), dtype=torch.int64, device=self.device)
-        if ok_out is None:
-            ok_out = torch.empty((B,), dtype=torch.uint8, device=self.device)
-        pe, pi, po = chk(env_out, (B,), torch.int32, "env_out"), chk(index_out, (B,), torch.int64, "index_out"), chk(ok_out, (B,), torch.uint8, "ok_out")
+        new = self.pipe._out
+        env_out, pe = new(env_out, (B,), torch.int32, "env_out")
+        index_out, pi = new(index_out, (B,), torch.int64, "index_out")
+        ok_out, po = new(ok_out, (B,), torch.uint8, "ok_out")
         self._check(self._lib.agx_replay_sample(self._r, B, pe, pi, po, _P(self._total.data_ptr()), self.pipe._stream()))
         return env_out, index_out, ok_out
 
@@ -139,34 +119,20 @@ class ReplaySampler:
     def transitions(self, B: int, glimpses: Optional[int] = None):
         """B transitions (index, index + forward) of one episode each, as a dict: env, index, next_index, ok, obs, next_obs and,
         on a fixed pipeline, fov_loc, next_fov_loc.  glimpses = None reads through history.observe; glimpses = P through
-        GlimpseMemory(history, P) (fov_loc is then [B, P, 2]) and needs back >= P - 1.  Rows with ok = 0 are left as allocated."""
+        history.memory(P) (fov_loc is then [B, P, 2]) and needs back >= P - 1.  Rows with ok = 0 are left as allocated."""
         check_transitions(self.back, self.forward, glimpses)
         env, index, ok = self.sample(B)
         next_index = torch.where(index >= 0, index + self.forward, index)
-        if glimpses is None:
-            obs, loc, _ = self.history.observe(env, index)
-            nobs, nloc, _ = self.history.observe(env, next_index)
-        else:
-            mem = self._mem.get(int(glimpses))
-            if mem is None:
-                from .glimpse import GlimpseMemory
-                mem = self._mem[int(glimpses)] = GlimpseMemory(self.history, glimpses)
-            obs, loc, _ = mem.observe(env, index)
-            nobs, nloc, _ = mem.observe(env, next_index)
-        out = {"env": env, "index": index, "next_index": next_index, "ok": ok, "obs": obs, "next_obs": nobs}
-        if self.pipe.kind == "fixed":
-            out["fov_loc"], out["next_fov_loc"] = loc, nloc
+        read = self.history.observe if glimpses is None else self.history.memory(glimpses).observe
+        out = {"env": env, "index": index, "next_index": next_index, "ok": ok}
+        out.update(self.history.transition_obs(read, env, index, next_index))
         return out
 
 
 def inspect(history, env: torch.Tensor, index: torch.Tensor):
     """agx_replay_inspect on a FrameHistory: needs no sampler."""
     pipe = history.pipe
-    if not isinstance(env, torch.Tensor) or env.dim() != 1:
-        raise ValueError("env must be a 1-D int32 tensor")
-    b = int(env.shape[0])
-    pe = pipe._chk(env, (b,), torch.int32, "env")
-    pi = pipe._chk(index, (b,), torch.int64, "index")
+    b, pe, pi = pipe._pair(env, index)
     age = torch.empty((b,), dtype=torch.int32, device=history.device)
     ahead = torch.empty((b,), dtype=torch.int32, device=history.device)
     nat.check(lib().agx_replay_inspect(history.handle, pe, pi, b, _P(age.data_ptr()), _P(ahead.data_ptr()), pipe._stream()), pipe._ctx)

@@ -23,9 +23,11 @@ from __future__ import annotations
 import ctypes as C
 from typing import Optional
 
+import numpy as np
 import torch
 
 from . import _native as nat
+from .lifetime import Owner
 
 _P = C.c_void_p
 PAYLOAD_LIMIT = 64                    # AGX_STEPLOG_PAYLOAD_LIMIT
@@ -75,7 +77,9 @@ def check_env_step_log(step_log, history_len, discrete_motor: bool = True) -> bo
     return on
 
 
-class StepLog:
+class StepLog(Owner):
+    _closed_what = "the step log or its history"
+
     def __init__(self, history, payload_bytes: int = 0):
         """history: a FrameHistory; payload_bytes: opaque bytes kept per row (0 .. 64, a multiple of 4), the action usually."""
         self.payload_bytes = check_payload_bytes(payload_bytes)
@@ -85,32 +89,10 @@ class StepLog:
         self.device = history.device
         self.num_envs = history.num_envs
         self._s = _P()
-        self._mem = {}
         nat.check(self._lib.agx_steplog_create(history.handle, self.payload_bytes, C.byref(self._s)), self.pipe._ctx)
-        # the log holds the history's raw handle: it goes before the history does (the pipeline closes its dependents in order)
-        deps = self.pipe._dependents
-        deps.insert(deps.index(history) if history in deps else 0, self)
-        # ... and the history clears it with itself: its indices restart there
-        history._steplogs = list(getattr(history, "_steplogs", ())) + [self]
-
-    def close(self):
-        if getattr(self, "_s", None) is not None and self._s.value:
-            self._lib.agx_steplog_destroy(self._s)
-            self._s = _P()
-            if self in getattr(self.pipe, "_dependents", ()):
-                self.pipe._dependents.remove(self)
-            if self in getattr(self.history, "_steplogs", ()):
-                self.history._steplogs.remove(self)
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:  # noqa: BLE001
-            pass
-
-    def _live(self):
-        if not self._s.value or not self.history.handle.value:
-            raise RuntimeError("the step log or its history is closed")
+        # the log holds the history's raw handle: it goes before the history does, which also clears it with itself (its
+        # indices restart there)
+        self._own(self._s, self._lib.agx_steplog_destroy, (history,))
 
     def _check(self, rc):
         nat.check(rc, self.pipe._ctx)
@@ -146,10 +128,8 @@ class StepLog:
         flags and payload are 0."""
         nstep = check_nstep(nstep)
         self._live()
-        if not isinstance(env, torch.Tensor) or env.dim() != 1:
-            raise ValueError("env must be a 1-D int32 tensor")
-        b, w, chk, dev = int(env.shape[0]), self.payload_bytes, self.pipe._chk, self.device
-        pe, pi = chk(env, (b,), torch.int32, "env"), chk(index, (b,), torch.int64, "index")
+        b, pe, pi = self.pipe._pair(env, index)
+        w, dev = self.payload_bytes, self.device
         out = {"ret": torch.zeros((b,), dtype=torch.float32, device=dev), "discount": torch.zeros((b,), dtype=torch.float32, device=dev),
                "steps": torch.empty((b,), dtype=torch.int32, device=dev), "next_index": torch.empty((b,), dtype=torch.int64, device=dev),
                "flags": torch.zeros((b,), dtype=torch.uint8, device=dev), "payload": torch.zeros((b, w), dtype=torch.uint8, device=dev)}
@@ -162,8 +142,8 @@ class StepLog:
         """``sampler.sample(B)``, ``gather``, then the observations at ``index`` (obs) and at ``next_index`` (next_obs), as one dict:
         env, index, next_index, ok, obs, next_obs, ret, discount, steps, flags, payload and, on a fixed pipeline, fov_loc and
         next_fov_loc.  ``ok`` is the sampler's ok AND steps > 0.  glimpses = None reads through history.observe; glimpses = P
-        through ``memory`` - a GlimpseMemory(history, P) the caller owns - or, without one, through one this log creates once per
-        P, and needs a sampler with back >= P - 1.  Rows with ok = 0 are left as allocated."""
+        through ``memory`` - a GlimpseMemory of P glimpses on this history that the caller owns - or, without one, through
+        ``history.memory(P)``, and needs a sampler with back >= P - 1.  Rows with ok = 0 are left as allocated."""
         nstep = check_nstep(nstep)
         if sampler.history is not self.history:
             raise ValueError("the sampler draws from another history than the one this log is on")
@@ -176,17 +156,50 @@ class StepLog:
         out = self.gather(env, index, nstep, gamma)
         if glimpses is None:
             read = self.history.observe
-        elif memory is not None:
-            read = memory.observe
         else:
-            mem = self._mem.get(int(glimpses))
-            if mem is None:
-                from .glimpse import GlimpseMemory
-                mem = self._mem[int(glimpses)] = GlimpseMemory(self.history, glimpses)
-            read = mem.observe
-        obs, loc, _ = read(env, index)
-        nobs, nloc, _ = read(env, out["next_index"])
-        out.update(env=env, index=index, ok=ok & (out["steps"] > 0).to(torch.uint8), obs=obs, next_obs=nobs)
-        if self.pipe.kind == "fixed":
-            out["fov_loc"], out["next_fov_loc"] = loc, nloc
+            read = (memory if memory is not None else self.history.memory(glimpses)).observe
+        obs = self.history.transition_obs(read, env, index, out["next_index"])
+        out.update(env=env, index=index, ok=ok & (out["steps"] > 0).to(torch.uint8))
+        out.update(obs)
         return out
+
+
+class EnvStepLog:
+    """A vector env's per-step upload into its StepLog: what the step returned on the host - motor action, reward, done -
+    travels in one pinned i32 [3, N] buffer; two sets (pinned, device, event), used alternately, each rewritten only after the
+    event behind its last copy.  The payload is the motor action as int32, followed on a fixed env by the sensory action as two
+    float32."""
+
+    def __init__(self, log: StepLog, fixed: bool, autoreset: bool):
+        self.log, self.autoreset = log, bool(autoreset)
+        n, dev = log.num_envs, log.device
+        self._sets = [(torch.empty((3, n), dtype=torch.int32, pin_memory=True), torch.empty((3, n), dtype=torch.int32, device=dev),
+                       torch.cuda.Event()) for _ in range(2)]
+        self._i = 0
+        self._payload = torch.empty((n, 3), dtype=torch.int32, device=dev) if fixed else None
+
+    def record(self, motor, sens, reward, done):
+        """Record what this step returned, after its pushes - one upload of (motor, reward, done), then device work only.  Row =
+        the newest index, or the one before it for an env that was autoreset in this step (its terminal observation: the reset
+        observation has no step behind it)."""
+        log = self.log
+        n = log.num_envs
+        h, d, ev = self._sets[self._i]
+        self._i ^= 1
+        ev.synchronize()                        # the copy that last read this pinned buffer, two steps ago
+        host = h.numpy()
+        host[0] = np.asarray(motor).reshape(n)          # (the cast the runner itself makes)
+        host[1] = np.asarray(reward, dtype=np.float32).reshape(n).view(np.int32)
+        host[2] = np.asarray(done, dtype=bool).reshape(n)
+        d.copy_(h, non_blocking=True)
+        ev.record()
+        index = log.history.last_index()
+        if self.autoreset:
+            index -= d[2]
+        if sens is None:
+            payload = d[0].reshape(n, 1)
+        else:
+            payload = self._payload
+            payload[:, 0] = d[0]
+            payload[:, 1:] = sens.to(torch.float32).view(torch.int32)
+        log.record(index, d[1].view(torch.float32), d[2].to(torch.uint8), payload.view(torch.uint8))      # TERMINATED == 1

@@ -97,11 +97,8 @@ class AtariVecEnv:
     history_len = 0
     steplog = None           # steplog.StepLog when args.step_log
     step_log = False
-    _log_sets = None         # step_log: two (pinned, device, event) sets of the per-step upload, used alternately
-    _log_i = 0
+    _env_log = None          # steplog.EnvStepLog when args.step_log: the per-step upload into it
     _discrete_motor = True   # the motor action is one integer per env (what the step log's payload holds)
-    _glimpse_of = None       # the history the cached glimpse.GlimpseMemory objects (by glimpses) read
-    _replay_of = None        # the history the cached replay.ReplaySampler objects (by argument tuple) read
 
     def __init__(self, args, num_envs: int, kind: str = "fixed", env_offset: int = 0, noop_fn=None,
                  autoreset: bool = True, noop_per_env: bool = False):
@@ -190,17 +187,12 @@ class AtariVecEnv:
         self._ragged_packed = kind == "flexible" and self._raw_crop and wants_packed(args)
         self.pipe = ObsPipeline(**kw)
         self.history = FrameHistory(self.pipe, self.history_len) if self.history_len > 0 else None
-        self.steplog = None
+        self.steplog = self._env_log = None
         if self.step_log:
-            from .steplog import StepLog
+            from .steplog import EnvStepLog, StepLog
             self.steplog = StepLog(self.history, 12 if kind == "fixed" else 4)      # motor i32 [, sensory 2 x f32]
-            # (motor, reward bits, done) of a step travel in one pinned i32 [3, N] buffer; two sets, used alternately, each
-            # rewritten only after the event behind its last copy
-            n = self.num_envs
-            self._log_sets = [{"h": torch.empty((3, n), dtype=torch.int32, pin_memory=True),
-                               "d": torch.empty((3, n), dtype=torch.int32, device=self.device),
-                               "ev": torch.cuda.Event()} for _ in range(2)]
-            self._log_payload = torch.empty((n, 3), dtype=torch.int32, device=self.device) if kind == "fixed" else None
+            self._env_log = EnvStepLog(self.steplog, kind == "fixed", self.autoreset)
+        self._env_ids = torch.arange(self.num_envs, dtype=torch.int32, device=self.device) if self.history is not None else None
 
     def _build_spaces(self):
         kind = self.kind
@@ -408,32 +400,6 @@ class AtariVecEnv:
         """i64 [N]: the history index of each env's newest observation (NumPy with host outputs)."""
         return self._out(self.history.last_index())
 
-    def _log_step(self, motor, sens, reward, done):
-        """args.step_log: record what this step returned, after its pushes - one upload of (motor, reward, done), then device
-        work only.  Row = the newest index, or the one before it for an env that was autoreset in this step (its terminal
-        observation: the reset observation has no step behind it)."""
-        n = self.num_envs
-        st = self._log_sets[self._log_i]
-        self._log_i ^= 1
-        st["ev"].synchronize()                  # the copy that last read this pinned buffer, two steps ago
-        host = st["h"].numpy()
-        host[0] = np.asarray(motor).reshape(n)          # (the cast the runner itself makes)
-        host[1] = np.asarray(reward, dtype=np.float32).reshape(n).view(np.int32)
-        host[2] = np.asarray(done, dtype=bool).reshape(n)
-        d = st["d"]
-        d.copy_(st["h"], non_blocking=True)
-        st["ev"].record()
-        index = self.history.last_index()
-        if self.autoreset:
-            index -= d[2]
-        if sens is None:
-            payload = d[0].reshape(n, 1)
-        else:
-            payload = self._log_payload
-            payload[:, 0] = d[0]
-            payload[:, 1:] = sens.to(torch.float32).view(torch.int32)
-        self.steplog.record(index, d[1].view(torch.float32), d[2].to(torch.uint8), payload.view(torch.uint8))      # TERMINATED == 1
-
     def replay_batch(self, B: int, nstep: int = 1, gamma: float = 0.99, glimpses: Optional[int] = None, **sampler_kw):
         """B learner rows from the env's step log: ``steplog.batch(env.replay_sampler(**sampler_kw), B, nstep, gamma, glimpses)``
         with the payload split into ``motor_action`` (i32 [B]) and, on a fixed env, ``sensory_action`` (f32 [B, 2]): the action
@@ -444,11 +410,10 @@ class AtariVecEnv:
         nstep = check_nstep(nstep)
         if self.steplog is None:
             raise ValueError("replay_batch needs a step log (AtariEnvArgs.step_log = True, history_len > 0)")
-        memory = None
         if glimpses is not None:
             sampler_kw.setdefault("back", int(glimpses) - 1)
-            memory = self._glimpse_mem(glimpses)                 # the env's own, shared with glimpse_memory()
-        out = self.steplog.batch(self.replay_sampler(**sampler_kw), B, nstep, gamma, glimpses, memory=memory)
+            self.history.memory(glimpses)                        # ValueError for a kind or mode that is not served, before a draw
+        out = self.steplog.batch(self.replay_sampler(**sampler_kw), B, nstep, gamma, glimpses)
         words = out.pop("payload").view(torch.int32)
         out["motor_action"] = words[:, 0].contiguous()
         if self.kind == "fixed":
@@ -457,41 +422,23 @@ class AtariVecEnv:
 
     def glimpse_memory(self, glimpses: int = 3, out: Optional[torch.Tensor] = None):
         """The glimpse memory of the observation the last ``reset`` / ``step`` returned, for all N envs: the elementwise
-        maximum over each env's last up-to-``glimpses`` observations since its last reset (glimpse.GlimpseMemory.observe at
+        maximum over each env's last up-to-``glimpses`` observations since its last reset (``history.memory(glimpses).observe`` at
         ``history.last_index()``; an env autoreset in the last step gives just its returned observation).  Needs
         ``history_len`` > 0, kind "fixed" and mask_out or resize_to_full mode: ValueError otherwise."""
-        obs, _, _ = self._glimpse_mem(glimpses).observe(self._glimpse_env, self.history.last_index(), out=out)
-        return self._out(obs)
-
-    def _glimpse_mem(self, glimpses: int):
-        """The env's glimpse.GlimpseMemory of ``glimpses`` glimpses on its history, cached per value."""
-        from .glimpse import GlimpseMemory
         if self.history is None:
             raise ValueError("glimpse_memory needs a frame history (AtariEnvArgs.history_len > 0)")
-        if self._glimpse_of is not self.history:                # a rebuilt pipeline (rekind) has a new history
-            self._glimpse_of, self._glimpse = self.history, {}
-            self._glimpse_env = torch.arange(self.num_envs, dtype=torch.int32, device=self.device)
-        mem = self._glimpse.get(int(glimpses))
-        if mem is None:
-            mem = self._glimpse[int(glimpses)] = GlimpseMemory(self.history, glimpses)      # ValueError for a kind or mode that is not served
-        return mem
+        obs, _, _ = self.history.memory(glimpses).observe(self._env_ids, self.history.last_index(), out=out)
+        return self._out(obs)
 
     def replay_sampler(self, back: int = 0, forward: int = 1, attempts: int = 16, seed: Optional[int] = None):
         """A replay.ReplaySampler on the env's frame history, cached per argument tuple: ``sample(B)`` draws (env, index) pairs
         that are retained, have ``back`` valid earlier glimpses of their episode and ``forward`` later appends of it, and
         ``transitions(B)`` re-creates both observations (index and index + forward never straddle a reset).  ``seed=None``
         takes ``args.seed``.  Needs ``history_len`` > 0: ValueError otherwise."""
-        from .replay import ReplaySampler
         if self.history is None:
             raise ValueError("replay_sampler needs a frame history (AtariEnvArgs.history_len > 0)")
-        if self._replay_of is not self.history:                 # a rebuilt pipeline (rekind) has a new history
-            self._replay_of, self._replay = self.history, {}
         seed = int(getattr(self.args, "seed", 0) or 0) if seed is None else int(seed)
-        key = (int(back), int(forward), int(attempts), seed)
-        smp = self._replay.get(key)
-        if smp is None:
-            smp = self._replay[key] = ReplaySampler(self.history, back, forward, attempts, seed)
-        return smp
+        return self.history.sampler(back, forward, attempts, seed)
 
     def _next_obs_buffer(self, keep=False):
         """Turn to the other output buffer; keep: with the current observations in it (before a masked observe: the envs that
@@ -631,23 +578,19 @@ class AtariVecEnv:
                     infos[key] = np.where(done.reshape((n,) + (1,) * (info[key].ndim - 1)), rinfo[key], info[key])
             attach_final(infos, done, *final)
         if self.steplog is not None:
-            self._log_step(motor, sens, reward, done)
+            self._env_log.record(motor, sens, reward, done)
         st.release()
         return self._ret_obs(obs), reward, done, truncated, infos
 
     def _step_native(self, motor, sens, stype):
         """step() through the native loop: one C call does emulators -> staging -> H2D -> ingest -> fovea -> autoreset; what is
         left here is the bookkeeping the reference's RecordWrapper / SyncVectorEnv do in Python (counters, info dicts)."""
-        from .pipeline import _DT
+        from .pipeline import action_dt
         from .runner import check_motor_actions
         n = self.num_envs
         motor = check_motor_actions(motor, self.runner.num_actions).reshape(n)
         self._next_obs_buffer()
-        dt = 0
-        if sens is not None:
-            if sens.dtype not in _DT:
-                raise TypeError(f"sensory action dtype {sens.dtype} not supported (f32/f64/i32/i64)")
-            dt = _DT[sens.dtype]
+        dt = action_dt(sens)
         # host outputs in env chunks (args.host_obs_chunks): straight into a pinned buffer, observations, fov rows and terminal
         # rows as NumPy; without a pinned destination (pool budget spent) this call is the unchunked step + copy
         h = self._host.take(self._obs) if self._host_step is not None else None
@@ -682,7 +625,7 @@ class AtariVecEnv:
         if final is not None:
             attach_final(infos, done, *final)
         if self.steplog is not None:
-            self._log_step(motor, sens, reward, done)
+            self._env_log.record(motor, sens, reward, done)
         obs = self._host.hand_out(h) if h is not None else self._ret_obs(self._obs)
         return obs, reward, done, truncated, infos
 

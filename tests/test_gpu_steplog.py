@@ -414,10 +414,14 @@ def test_vec_env_replay_batch(native):
         env.replay_batch(8, nstep=0)
     # glimpses = P reads through the env's own glimpse memory (the one glimpse_memory(P) uses), not a second one
     gb = env.replay_batch(64, nstep=3, gamma=GAMMA, glimpses=3)
-    assert env.steplog._mem == {} and list(env._glimpse) == [3] and env.replay_sampler(back=2).back == 2
+    mem, used = env.history._memories[3], []
+    mem.observe = lambda *a, _observe=mem.observe, **kw: used.append(mem) or _observe(*a, **kw)       # spy: who serves glimpse_memory(3)
+    env.glimpse_memory(3)
+    del mem.observe
+    assert list(env.history._memories) == [3] and used == [mem] and env.replay_sampler(back=2).back == 2
     rows = gb["ok"].bool()
     assert rows.any() and tuple(gb["fov_loc"].shape) == (64, 3, 2)
-    ref, _, _ = env._glimpse[3].observe(gb["env"], gb["next_index"])
+    ref, _, _ = env.history.memory(3).observe(gb["env"], gb["next_index"])
     assert torch.equal(gb["next_obs"][rows].view(torch.int32), ref[rows].view(torch.int32))
     env.close()
 
