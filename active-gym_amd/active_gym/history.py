@@ -93,11 +93,12 @@ class FrameHistory(Owner):
 
     def clear(self):
         """Every index becomes invalid, the per-env indices restart at 0.  The step logs on this history are cleared with it (a
-        row recorded before the clear must not pass for one of a new index)."""
+        row recorded before the clear must not pass for one of a new index), and so are the prioritized samplers' tables."""
         self._check(self._lib.agx_history_clear(self._h, self.pipe._stream()))
+        from .priority import PrioritizedSampler
         from .steplog import StepLog
         for child in self._children:
-            if isinstance(child, StepLog):          # (a sampler keeps no rows)
+            if isinstance(child, (StepLog, PrioritizedSampler)):          # (a uniform sampler keeps no rows)
                 child.clear()
 
     def push(self, cmd: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -158,6 +159,15 @@ class FrameHistory(Owner):
         if smp is None:
             from .replay import ReplaySampler
             smp = self._samplers[key] = ReplaySampler(self, back, forward, attempts, seed)
+        return smp
+
+    def prioritized(self, back: int = 0, forward: int = 1, seed: int = 0):
+        """The one priority.PrioritizedSampler of this argument tuple on this history, made at first use."""
+        key = ("prioritized", int(back), int(forward), int(seed))
+        smp = self._samplers.get(key)
+        if smp is None:
+            from .priority import PrioritizedSampler
+            smp = self._samplers[key] = PrioritizedSampler(self, back, forward, seed)
         return smp
 
     def transition_obs(self, read, env, index, next_index) -> dict:

@@ -1,5 +1,5 @@
-"""Owner — the one place that keeps a raw C handle alive and destroys it: for the six classes that hold one (ObsPipeline,
-NativeHostRunner, NativeStepLoop, FrameHistory, ReplaySampler, StepLog).
+"""Owner — the one place that keeps a raw C handle alive and destroys it: for the seven classes that hold one (ObsPipeline,
+NativeHostRunner, NativeStepLoop, FrameHistory, ReplaySampler, StepLog, PrioritizedSampler).
 
 An object that was built from the raw handles of others names them as its parents and must be gone before any of them is.  The
 tree is

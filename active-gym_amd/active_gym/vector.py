@@ -98,6 +98,7 @@ class AtariVecEnv:
     steplog = None           # steplog.StepLog when args.step_log
     step_log = False
     _env_log = None          # steplog.EnvStepLog when args.step_log: the per-step upload into it
+    _per = None              # priority.PrioritizedSampler the last prioritized replay_batch drew from
     _discrete_motor = True   # the motor action is one integer per env (what the step log's payload holds)
 
     def __init__(self, args, num_envs: int, kind: str = "fixed", env_offset: int = 0, noop_fn=None,
@@ -187,7 +188,7 @@ class AtariVecEnv:
         self._ragged_packed = kind == "flexible" and self._raw_crop and wants_packed(args)
         self.pipe = ObsPipeline(**kw)
         self.history = FrameHistory(self.pipe, self.history_len) if self.history_len > 0 else None
-        self.steplog = self._env_log = None
+        self.steplog = self._env_log = self._per = None      # (the samplers are cached on the history: rebuilt with it)
         if self.step_log:
             from .steplog import EnvStepLog, StepLog
             self.steplog = StepLog(self.history, 12 if kind == "fixed" else 4)      # motor i32 [, sensory 2 x f32]
@@ -400,12 +401,16 @@ class AtariVecEnv:
         """i64 [N]: the history index of each env's newest observation (NumPy with host outputs)."""
         return self._out(self.history.last_index())
 
-    def replay_batch(self, B: int, nstep: int = 1, gamma: float = 0.99, glimpses: Optional[int] = None, **sampler_kw):
+    def replay_batch(self, B: int, nstep: int = 1, gamma: float = 0.99, glimpses: Optional[int] = None, prioritized: bool = False,
+                     beta: float = 0.4, **sampler_kw):
         """B learner rows from the env's step log: ``steplog.batch(env.replay_sampler(**sampler_kw), B, nstep, gamma, glimpses)``
         with the payload split into ``motor_action`` (i32 [B]) and, on a fixed env, ``sensory_action`` (f32 [B, 2]): the action
         taken on seeing ``obs``.  ``ret`` / ``discount`` / ``next_obs`` are the n-step target's parts: target = ret + discount *
         value(next_obs).  ``glimpses = P`` reads the observations through the glimpse memory (the sampler's ``back`` defaults to
-        P - 1 then).  Rows with ok = 0 are to be ignored.  Needs ``step_log``: ValueError otherwise."""
+        P - 1 then).  ``prioritized=True`` draws through ``env.prioritized_sampler(**sampler_kw)`` instead and adds ``weight``
+        (f32 [B], the importance weights at ``beta``) and ``priority`` (i64 [B], the drawn integer weights);
+        ``env.update_priorities(batch, td_error)`` writes the new priorities back.  Rows with ok = 0 are to be ignored.  Needs
+        ``step_log``: ValueError otherwise."""
         from .steplog import check_nstep
         nstep = check_nstep(nstep)
         if self.steplog is None:
@@ -413,12 +418,30 @@ class AtariVecEnv:
         if glimpses is not None:
             sampler_kw.setdefault("back", int(glimpses) - 1)
             self.history.memory(glimpses)                        # ValueError for a kind or mode that is not served, before a draw
-        out = self.steplog.batch(self.replay_sampler(**sampler_kw), B, nstep, gamma, glimpses)
+        if prioritized:
+            sampler = self._per = self.prioritized_sampler(**sampler_kw)
+        else:
+            sampler = self.replay_sampler(**sampler_kw)
+        out = self.steplog.batch(sampler, B, nstep, gamma, glimpses)
         words = out.pop("payload").view(torch.int32)
         out["motor_action"] = words[:, 0].contiguous()
         if self.kind == "fixed":
             out["sensory_action"] = words[:, 1:3].contiguous().view(torch.float32)
+        if prioritized:
+            out["weight"], out["priority"] = sampler.importance(beta), sampler.weight
         return out
+
+    def update_priorities(self, batch: dict, td_error: torch.Tensor, alpha: float = 0.6, eps: float = 1e-6, **sampler_kw):
+        """Write priority = (|td_error| + eps) ** alpha for the rows of a ``replay_batch(..., prioritized=True)`` batch; rows with
+        ok = 0 are skipped, and so are rows evicted since the draw.  The table is that of the sampler the last prioritized
+        ``replay_batch`` drew from, or of ``env.prioritized_sampler(**sampler_kw)`` where arguments are given."""
+        sampler = self.prioritized_sampler(**sampler_kw) if sampler_kw else self._per
+        if sampler is None:
+            raise ValueError("update_priorities needs a batch of replay_batch(..., prioritized=True), or the sampler's arguments")
+        skip = batch["ok"] == 0
+        env = torch.where(skip, torch.full_like(batch["env"], -1), batch["env"])
+        index = torch.where(skip, torch.full_like(batch["index"], -1), batch["index"])
+        sampler.update_td(env, index, td_error, alpha, eps)
 
     def glimpse_memory(self, glimpses: int = 3, out: Optional[torch.Tensor] = None):
         """The glimpse memory of the observation the last ``reset`` / ``step`` returned, for all N envs: the elementwise
@@ -439,6 +462,15 @@ class AtariVecEnv:
             raise ValueError("replay_sampler needs a frame history (AtariEnvArgs.history_len > 0)")
         seed = int(getattr(self.args, "seed", 0) or 0) if seed is None else int(seed)
         return self.history.sampler(back, forward, attempts, seed)
+
+    def prioritized_sampler(self, back: int = 0, forward: int = 1, seed: Optional[int] = None):
+        """A priority.PrioritizedSampler on the env's frame history, cached per argument tuple: ``sample(B)`` draws the pairs
+        ``replay_sampler`` accepts with probability proportional to their priority, ``update_td`` sets priorities.  ``seed=None``
+        takes ``args.seed``.  Needs ``history_len`` > 0: ValueError otherwise."""
+        if self.history is None:
+            raise ValueError("prioritized_sampler needs a frame history (AtariEnvArgs.history_len > 0)")
+        seed = int(getattr(self.args, "seed", 0) or 0) if seed is None else int(seed)
+        return self.history.prioritized(back, forward, seed)
 
     def _next_obs_buffer(self, keep=False):
         """Turn to the other output buffer; keep: with the current observations in it (before a masked observe: the envs that
