@@ -71,10 +71,10 @@ class FrameHistory(Owner):
         self.num_envs = pipe.num_envs
         self._h = _P()
         nat.check(self._lib.agx_history_create(pipe._ctx, self.capacity, C.byref(self._h)), pipe._ctx)
-        # the history holds the context's raw handle: it goes before the pipeline does; the samplers and step logs on it are
-        # its children and go before it
+        # the history holds the context's raw handle: it goes before the pipeline does; the samplers, step logs and shift sources on it
+        # are its children and go before it
         self._own(self._h, self._lib.agx_history_destroy, (pipe,))
-        self._memories, self._samplers = {}, {}
+        self._memories, self._samplers, self._shifts = {}, {}, {}
 
     @property
     def handle(self):
@@ -170,12 +170,27 @@ class FrameHistory(Owner):
             smp = self._samplers[key] = PrioritizedSampler(self, back, forward, seed)
         return smp
 
-    def transition_obs(self, read, env, index, next_index) -> dict:
+    def shift(self, pad: int = 4, seed: int = 0):
+        """The one augment.RandomShift of this argument tuple on this history, made at first use."""
+        key = (int(pad), int(seed))
+        aug = self._shifts.get(key)
+        if aug is None:
+            from .augment import RandomShift
+            aug = self._shifts[key] = RandomShift(self, pad, seed)
+        return aug
+
+    def transition_obs(self, read, env, index, next_index, shift=None) -> dict:
         """The observation part of a transition batch through ``read`` (``self.observe`` or a GlimpseMemory's): obs, next_obs
-        and, on a fixed pipeline, fov_loc, next_fov_loc."""
+        and, on a fixed pipeline, fov_loc, next_fov_loc.  ``shift``: the augment.RandomShift whose ``observe`` ``read`` is - two
+        independent draws, obs first; the shifts of each are added as obs_shift and next_obs_shift (i32 [B, 2])."""
         obs, loc, _ = read(env, index)
+        out = {"obs": obs}
+        if shift is not None:
+            out["obs_shift"] = shift.last_shift
         nobs, nloc, _ = read(env, next_index)
-        out = {"obs": obs, "next_obs": nobs}
+        out["next_obs"] = nobs
+        if shift is not None:
+            out["next_obs_shift"] = shift.last_shift
         if self.pipe.kind == "fixed":
             out["fov_loc"], out["next_fov_loc"] = loc, nloc
         return out

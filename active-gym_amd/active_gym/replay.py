@@ -116,16 +116,23 @@ class ReplaySampler(Owner):
         appends of its episode already in the history (what an n-step target needs); -1, -1 for an invalid sample."""
         return inspect(self.history, env, index)
 
-    def transitions(self, B: int, glimpses: Optional[int] = None):
+    def transitions(self, B: int, glimpses: Optional[int] = None, shift=None):
         """B transitions (index, index + forward) of one episode each, as a dict: env, index, next_index, ok, obs, next_obs and,
         on a fixed pipeline, fov_loc, next_fov_loc.  glimpses = None reads through history.observe; glimpses = P through
-        history.memory(P) (fov_loc is then [B, P, 2]) and needs back >= P - 1.  Rows with ok = 0 are left as allocated."""
+        history.memory(P) (fov_loc is then [B, P, 2]) and needs back >= P - 1.  shift: an augment.RandomShift on this history -
+        obs and next_obs are read through it, two independent draws, and the dict gains obs_shift and next_obs_shift (not
+        together with glimpses).  Rows with ok = 0 are left as allocated."""
         check_transitions(self.back, self.forward, glimpses)
+        from .augment import check_shift_read
+        check_shift_read(shift, glimpses, self.history)
         env, index, ok = self.sample(B)
         next_index = torch.where(index >= 0, index + self.forward, index)
-        read = self.history.observe if glimpses is None else self.history.memory(glimpses).observe
+        if shift is not None:
+            read = shift.observe
+        else:
+            read = self.history.observe if glimpses is None else self.history.memory(glimpses).observe
         out = {"env": env, "index": index, "next_index": next_index, "ok": ok}
-        out.update(self.history.transition_obs(read, env, index, next_index))
+        out.update(self.history.transition_obs(read, env, index, next_index, shift))
         return out
 
 

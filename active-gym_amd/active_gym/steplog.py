@@ -138,13 +138,17 @@ class StepLog(Owner):
                                                  p["flags"], p["payload"] if w > 0 else None, self.pipe._stream()))
         return out
 
-    def batch(self, sampler, B: int, nstep: int = 1, gamma: float = 0.99, glimpses: Optional[int] = None, memory=None):
+    def batch(self, sampler, B: int, nstep: int = 1, gamma: float = 0.99, glimpses: Optional[int] = None, memory=None, shift=None):
         """``sampler.sample(B)``, ``gather``, then the observations at ``index`` (obs) and at ``next_index`` (next_obs), as one dict:
         env, index, next_index, ok, obs, next_obs, ret, discount, steps, flags, payload and, on a fixed pipeline, fov_loc and
         next_fov_loc.  ``ok`` is the sampler's ok AND steps > 0.  glimpses = None reads through history.observe; glimpses = P
         through ``memory`` - a GlimpseMemory of P glimpses on this history that the caller owns - or, without one, through
-        ``history.memory(P)``, and needs a sampler with back >= P - 1.  Rows with ok = 0 are left as allocated."""
+        ``history.memory(P)``, and needs a sampler with back >= P - 1.  shift: an augment.RandomShift on this history - obs and
+        next_obs are read through it, two independent draws in that order, and the dict gains obs_shift and next_obs_shift (not
+        together with glimpses).  Rows with ok = 0 are left as allocated."""
         nstep = check_nstep(nstep)
+        from .augment import check_shift_read
+        check_shift_read(shift, glimpses, self.history)
         if sampler.history is not self.history:
             raise ValueError("the sampler draws from another history than the one this log is on")
         if memory is not None and (glimpses is None or memory.history is not self.history or memory.glimpses != int(glimpses)):
@@ -154,11 +158,13 @@ class StepLog(Owner):
                              f"got back = {sampler.back}")
         env, index, ok = sampler.sample(B)
         out = self.gather(env, index, nstep, gamma)
-        if glimpses is None:
+        if shift is not None:
+            read = shift.observe
+        elif glimpses is None:
             read = self.history.observe
         else:
             read = (memory if memory is not None else self.history.memory(glimpses)).observe
-        obs = self.history.transition_obs(read, env, index, out["next_index"])
+        obs = self.history.transition_obs(read, env, index, out["next_index"], shift)
         out.update(env=env, index=index, ok=ok & (out["steps"] > 0).to(torch.uint8))
         out.update(obs)
         return out

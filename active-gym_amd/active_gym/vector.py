@@ -188,7 +188,7 @@ class AtariVecEnv:
         self._ragged_packed = kind == "flexible" and self._raw_crop and wants_packed(args)
         self.pipe = ObsPipeline(**kw)
         self.history = FrameHistory(self.pipe, self.history_len) if self.history_len > 0 else None
-        self.steplog = self._env_log = self._per = None      # (the samplers are cached on the history: rebuilt with it)
+        self.steplog = self._env_log = self._per = None      # (the samplers and shift sources are cached on the history: rebuilt with it)
         if self.step_log:
             from .steplog import EnvStepLog, StepLog
             self.steplog = StepLog(self.history, 12 if kind == "fixed" else 4)      # motor i32 [, sensory 2 x f32]
@@ -402,17 +402,23 @@ class AtariVecEnv:
         return self._out(self.history.last_index())
 
     def replay_batch(self, B: int, nstep: int = 1, gamma: float = 0.99, glimpses: Optional[int] = None, prioritized: bool = False,
-                     beta: float = 0.4, **sampler_kw):
+                     beta: float = 0.4, shift_pad: Optional[int] = None, **sampler_kw):
         """B learner rows from the env's step log: ``steplog.batch(env.replay_sampler(**sampler_kw), B, nstep, gamma, glimpses)``
         with the payload split into ``motor_action`` (i32 [B]) and, on a fixed env, ``sensory_action`` (f32 [B, 2]): the action
         taken on seeing ``obs``.  ``ret`` / ``discount`` / ``next_obs`` are the n-step target's parts: target = ret + discount *
         value(next_obs).  ``glimpses = P`` reads the observations through the glimpse memory (the sampler's ``back`` defaults to
         P - 1 then).  ``prioritized=True`` draws through ``env.prioritized_sampler(**sampler_kw)`` instead and adds ``weight``
         (f32 [B], the importance weights at ``beta``) and ``priority`` (i64 [B], the drawn integer weights);
-        ``env.update_priorities(batch, td_error)`` writes the new priorities back.  Rows with ok = 0 are to be ignored.  Needs
-        ``step_log``: ValueError otherwise."""
+        ``env.update_priorities(batch, td_error)`` writes the new priorities back.  ``shift_pad = p`` reads ``obs`` and
+        ``next_obs`` through ``env.random_shift(p)`` - DrQ's random shift, drawn independently for the two - and adds
+        ``obs_shift`` / ``next_obs_shift`` (i32 [B, 2]); not together with ``glimpses``.  Rows with ok = 0 are to be ignored.
+        Needs ``step_log``: ValueError otherwise."""
+        from .augment import check_no_glimpses, check_pad
         from .steplog import check_nstep
         nstep = check_nstep(nstep)
+        if shift_pad is not None:
+            check_pad(shift_pad)
+            check_no_glimpses(glimpses)
         if self.steplog is None:
             raise ValueError("replay_batch needs a step log (AtariEnvArgs.step_log = True, history_len > 0)")
         if glimpses is not None:
@@ -422,7 +428,7 @@ class AtariVecEnv:
             sampler = self._per = self.prioritized_sampler(**sampler_kw)
         else:
             sampler = self.replay_sampler(**sampler_kw)
-        out = self.steplog.batch(sampler, B, nstep, gamma, glimpses)
+        out = self.steplog.batch(sampler, B, nstep, gamma, glimpses, shift=None if shift_pad is None else self.random_shift(shift_pad))
         words = out.pop("payload").view(torch.int32)
         out["motor_action"] = words[:, 0].contiguous()
         if self.kind == "fixed":
@@ -462,6 +468,15 @@ class AtariVecEnv:
             raise ValueError("replay_sampler needs a frame history (AtariEnvArgs.history_len > 0)")
         seed = int(getattr(self.args, "seed", 0) or 0) if seed is None else int(seed)
         return self.history.sampler(back, forward, attempts, seed)
+
+    def random_shift(self, pad: int = 4, seed: Optional[int] = None):
+        """An augment.RandomShift on the env's frame history, cached per argument tuple: ``observe(env, index)`` is
+        ``history.observe`` with every sample moved by a freshly drawn shift of up to ``pad`` pixels either way.  ``seed=None``
+        takes ``args.seed``.  Needs ``history_len`` > 0: ValueError otherwise."""
+        if self.history is None:
+            raise ValueError("random_shift needs a frame history (AtariEnvArgs.history_len > 0)")
+        seed = int(getattr(self.args, "seed", 0) or 0) if seed is None else int(seed)
+        return self.history.shift(pad, seed)
 
     def prioritized_sampler(self, back: int = 0, forward: int = 1, seed: Optional[int] = None):
         """A priority.PrioritizedSampler on the env's frame history, cached per argument tuple: ``sample(B)`` draws the pairs

@@ -1,0 +1,146 @@
+// agx_augment_impl.h - the random-shift augmentation declared in include/agx_augment.h (included at the end of agx_api.hip,
+// behind the frame history it reads): the checks, the shift source's own scratch and the launches of agx_k10_augment.h.
+#pragma once
+#include "agx_augment.h"
+
+struct agx_shift {
+    agx_history *h = nullptr;
+    int device = 0;                 // the history's device: destroy needs no live history
+    int32_t pad = 0;
+    uint64_t *state = nullptr;      // the one device allocation: u64 [3] seed, calls, the draw launch's ticket counter
+};
+
+namespace {
+
+constexpr size_t kShiftStateBytes = 256;
+
+int shift_bad_pad(agx_ctx *ctx, const char *who, int32_t pad) {
+    return fail(ctx, AGX_E_INVALID, "%s: pad must be 0 .. %d, got %d", who, AGX_SHIFT_PAD_LIMIT, pad);
+}
+
+}  // namespace
+
+extern "C" {
+
+int agx_shift_create(agx_history *h, int32_t pad, agx_shift **out) {
+    agx_ctx *ctx = h ? h->ctx : nullptr;          // (no history: the message goes to agx_last_error(NULL))
+    if (out) *out = nullptr;
+    if (pad < 0 || pad > AGX_SHIFT_PAD_LIMIT) return shift_bad_pad(ctx, "agx_shift_create", pad);
+    if (!out) return fail(ctx, AGX_E_INVALID, "agx_shift_create: null out");
+    if (!h) return fail(ctx, AGX_E_INVALID, "agx_shift_create: null h");
+    if (!full_range(ctx)) return hist_refuse_range(h, "agx_shift_create");
+    agx_shift *s = new (std::nothrow) agx_shift;
+    if (!s) return fail(ctx, AGX_E_NOMEM, "out of host memory");
+    s->h = h;
+    s->device = ctx->cfg.device;
+    s->pad = pad;
+    DeviceGuard g(s->device);
+    hipError_t e = hipMalloc(reinterpret_cast<void **>(&s->state), kShiftStateBytes);
+    if (e == hipSuccess) e = hipMemset(s->state, 0, kShiftStateBytes);          // seed 0, calls 0, no ticket taken
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        if (s->state) (void)hipFree(s->state);
+        delete s;
+        return fail(ctx, e == hipErrorOutOfMemory ? AGX_E_NOMEM : AGX_E_HIP, "agx_shift_create: %zu bytes of device memory: %s", kShiftStateBytes,
+                    hipGetErrorString(e));
+    }
+    *out = s;
+    return AGX_OK;
+}
+
+int agx_shift_destroy(agx_shift *s) {
+    if (!s) return AGX_OK;
+    DeviceGuard g(s->device);
+    if (s->state) (void)hipFree(s->state);
+    delete s;
+    return AGX_OK;
+}
+
+int agx_shift_seed(agx_shift *s, uint64_t seed, void *stream) {
+    if (!s) return fail(nullptr, AGX_E_INVALID, "agx_shift_seed: null s");
+    agx_ctx *ctx = s->h->ctx;
+    if (!full_range(ctx)) return hist_refuse_range(s->h, "agx_shift_seed");
+    DeviceGuard g(s->device);
+    hipLaunchKernelGGL(agx::k_shift_seed, dim3(1), dim3(64), 0, S(stream), s->state, seed);
+    AGX_HIP(ctx, hipGetLastError());
+    return AGX_OK;
+}
+
+int agx_shift_draw(agx_shift *s, int32_t B, int32_t *d_shift, void *stream) {
+    agx_ctx *ctx = s ? s->h->ctx : nullptr;       // (the argument checks need no source: they come first)
+    if (B < 0) return fail(ctx, AGX_E_INVALID, "agx_shift_draw: B = %d", B);
+    if (B > 0 && !d_shift) return fail(ctx, AGX_E_INVALID, "agx_shift_draw: null d_shift");
+    if (!s) return fail(ctx, AGX_E_INVALID, "agx_shift_draw: null s");
+    if (!full_range(ctx)) return hist_refuse_range(s->h, "agx_shift_draw");
+    if (B == 0) return AGX_OK;
+    DeviceGuard g(s->device);
+    hipLaunchKernelGGL(agx::k_shift_draw, dim3((B + kThreads - 1) / kThreads), dim3(kThreads), 0, S(stream), s->state, s->pad, B, d_shift);
+    AGX_HIP(ctx, hipGetLastError());
+    return AGX_OK;
+}
+
+int agx_history_observe_shifted(agx_history *h, int what, const int32_t *d_env, const int64_t *d_index, int32_t B, const void *d_action,
+                                int action_dtype, int32_t pad, const int32_t *d_shift, float *d_obs, int32_t *d_fov_loc, uint8_t *d_valid,
+                                void *stream) {
+    agx_ctx *ctx = h ? h->ctx : nullptr;          // (the argument checks need no history: they come first)
+    if (what != AGX_HIST_FOVEA && what != AGX_HIST_FULL)
+        return fail(ctx, AGX_E_INVALID, "agx_history_observe_shifted: what must be AGX_HIST_FOVEA or AGX_HIST_FULL, got %d", what);
+    if (pad < 0 || pad > AGX_SHIFT_PAD_LIMIT) return shift_bad_pad(ctx, "agx_history_observe_shifted", pad);
+    if (B < 0) return fail(ctx, AGX_E_INVALID, "agx_history_observe_shifted: B = %d", B);
+    if (B > 0) {
+        if (!d_env) return fail(ctx, AGX_E_INVALID, "agx_history_observe_shifted: null d_env");
+        if (!d_index) return fail(ctx, AGX_E_INVALID, "agx_history_observe_shifted: null d_index");
+        if (!d_shift) return fail(ctx, AGX_E_INVALID, "agx_history_observe_shifted: null d_shift");
+        if (!d_obs) return fail(ctx, AGX_E_INVALID, "agx_history_observe_shifted: null d_obs");
+    }
+    int rc = check_dt(ctx, d_action, action_dtype);
+    if (rc) return rc;
+    if (!h) return fail(ctx, AGX_E_INVALID, "agx_history_observe_shifted: null h");
+    const agx_config &c = ctx->cfg;
+    if (what == AGX_HIST_FOVEA && c.kind != AGX_KIND_FIXED)
+        return fail(ctx, AGX_E_STATE, "agx_history_observe_shifted: AGX_HIST_FOVEA on a context without a fovea (a base context takes AGX_HIST_FULL only)");
+    if (B == 0) return AGX_OK;                    // (before the range check, as in agx_history_observe)
+    if (!full_range(ctx)) return hist_refuse_range(h, "agx_history_observe_shifted");
+    DeviceGuard g(c.device);
+    const bool fixed = c.kind == AGX_KIND_FIXED;
+    FovParams p = fov_params(ctx, fixed ? d_action : nullptr, action_dtype, nullptr, nullptr, d_obs, fixed ? d_fov_loc : nullptr, nullptr);
+    p.relative = 0;            // a read-time action is absolute whatever the context's action mode
+    p.ring = nullptr;
+    p.head = nullptr;
+    p.loc_in = p.loc_out = nullptr;
+    agx::HistObsParams q;
+    q.h = h->p;
+    q.has_loc = fixed ? 1 : 0;
+    agx::ShiftObsParams sh;
+    sh.pad = pad;
+    const bool fovea = what == AGX_HIST_FOVEA;
+    const size_t lds = fovea ? ctx->plan.lds : 0;
+    const size_t row_bytes = obs_row_bytes(ctx, fovea && c.out_mode == AGX_OUT_RAW);
+    // the sample index rides on gridDim.y: launches of at most 65535 samples, every per-sample array advanced with them
+    for (int32_t at = 0; at < B; at += 65535) {
+        const int nb = std::min<int32_t>(B - at, 65535);
+        FovParams pp = p;
+        pp.obs = reinterpret_cast<float *>(reinterpret_cast<char *>(d_obs) + (size_t)at * row_bytes);
+        if (pp.action) pp.action = static_cast<const char *>(pp.action) + (size_t)at * action_stride(action_dtype);
+        if (pp.user_loc) pp.user_loc += 2 * (size_t)at;
+        q.env = d_env + at;
+        q.index = d_index + at;
+        q.valid = d_valid ? d_valid + at : nullptr;
+        sh.shift = d_shift + 2 * (size_t)at;
+        const dim3 grid(c.frame_stack, nb), block(kThreads);
+        with_obs_type(ctx->obs_type, [&](auto tag) {
+            return with_geom(ctx->plan.headline, geom_r(c), [&](auto g) {
+                auto launch = [&](auto mode) {
+                    hipLaunchKernelGGL((agx::k_history_observe_shifted<decltype(g), decltype(mode)::value, decltype(tag)>), grid, block, lds, S(stream), g, pp,
+                                       q, sh);
+                    return 0;
+                };
+                return fovea ? with_mode(c.out_mode, launch) : launch(std::integral_constant<int, agx::kHistFull>{});
+            });
+        });
+    }
+    AGX_HIP(ctx, hipGetLastError());
+    return AGX_OK;
+}
+
+}  // extern "C"

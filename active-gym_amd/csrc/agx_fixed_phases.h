@@ -6,6 +6,7 @@
 #include "agx_common.h"
 #include "agx_glimpse.h"
 #include "agx_obs_store.h"
+#include "agx_shift_math.h"
 
 namespace agx {
 
@@ -105,6 +106,26 @@ __device__ __forceinline__ void phase_c(float *H, const unsigned char *win, cons
             const Tap t = xtab[x];
             H[i] = fmaf(t.b, unit_fast((float)win[y * ow + t.aux]), t.a * unit_fast((float)win[y * ow + t.lo]));
         }
+    }
+}
+
+// ---- the shifted siblings (agx_k10_augment.h): output row y takes the row tap of source row shift_src(y, dy, pad, oh), output
+// column x the column tap of source column shift_src(x, dx, pad, ow) - a move of whole H columns and whole output rows, so the
+// arithmetic of phase C / D and its bits are unchanged.  yt0 = ytab[shift_src(min(tid, oh - 1), ..)], xt = xtab[shift_src(xcol, ..)].
+__device__ __forceinline__ void ytab_stage_shifted(Tap *ytab_s, const int4 &yt0, const Tap *ytab, int oh, int tid, int dy, int pad) {
+    if (tid < oh) *reinterpret_cast<int4 *>(ytab_s + tid) = yt0;
+    for (int i = tid + kThreads; i < oh; i += kThreads) ytab_s[i] = ytab[shift_src(i, dy, pad, oh)];
+}
+__device__ __forceinline__ void phase_c_shifted(float *H, const unsigned char *win, const int4 &xt, const Tap *xtab, int ow, int fh,
+                                                int xcol, int yb, int tid, int dx, int pad) {
+    if (kThreads / ow > 0) {                                          // the register-tap form: phase_c itself on the shifted xt
+        phase_c(H, win, xt, xtab, ow, fh, xcol, yb, tid);
+        return;
+    }
+    for (int i = tid; i < fh * ow; i += kThreads) {                   // ow > 256: phase_c's striding form on xtab[cx(x)]
+        const int y = i / ow, x = i - y * ow;
+        const Tap t = xtab[shift_src(x, dx, pad, ow)];
+        H[i] = fmaf(t.b, unit_fast((float)win[y * ow + t.aux]), t.a * unit_fast((float)win[y * ow + t.lo]));
     }
 }
 
