@@ -15,7 +15,8 @@ Row ``k`` of an env holds the data of the step that PRODUCED observation ``k``: 
 reward received and the end flags of ``k``.  ``gather`` folds rows ``k + 1 .. k + nstep`` of sample ``(env, k)`` and stops at the
 episode's end, at a reset, at the end of the history and at a row that was never recorded: a sample with no such row has
 ``steps = 0`` and its other outputs are left untouched.  The fold is single precision with one rounding per operation;
-``tests/steplog_model.py`` restates it in NumPy.
+``tests/steplog_model.py`` restates it in NumPy.  Sequences of L consecutive steps, for recurrent learners, are read through
+``active_gym/sequence.py`` (SequenceReplay) on the same log.
 
 The entry points live in libagx.so, in a header and a binding of their own (active_gym/_native.py is unchanged)."""
 from __future__ import annotations

@@ -437,6 +437,40 @@ class AtariVecEnv:
             out["weight"], out["priority"] = sampler.importance(beta), sampler.weight
         return out
 
+    def sequence_batch(self, B: int, length: int, nstep: int = 1, gamma: float = 0.99, min_length: Optional[int] = None,
+                       prioritized: bool = False, beta: float = 0.4, planes: Optional[int] = None, time_major: bool = False, **sampler_kw):
+        """B sequences of ``length`` consecutive steps of one episode each, for a recurrent learner:
+        ``sequence.SequenceReplay(env.steplog).batch(...)`` with the starts drawn by ``env.replay_sampler(forward = (min_length or
+        length) - 1, **sampler_kw)``, so that every ok sequence has at least ``min_length`` live steps; a sampler guarantees at
+        most 65, so a longer ``length`` needs ``min_length`` (ValueError otherwise) and its sequences are padded where the episode
+        or the history ends.  Per step ([B, length], or [length, B] with ``time_major``): ``obs`` (``planes`` newest stacked
+        frames, None: all), ``live``, ``fov_loc``, ``steps`` / ``next_index`` / ``next_step`` / ``ret`` / ``discount`` / ``flags``
+        of the n-step target, and the payload split into ``motor_action`` (i32) and, on a fixed env, ``sensory_action`` (f32
+        [.., 2]): the action taken on seeing that step's observation.  Padded steps are zeros.  ``prioritized=True`` draws through
+        ``env.prioritized_sampler`` and adds ``weight`` / ``priority`` as ``replay_batch`` does;
+        ``env.update_priorities(batch, sequence.mixed_priority(td_abs, batch["live"]))`` writes a sequence's priority back to
+        its start.  Needs ``step_log``: ValueError otherwise."""
+        from .sequence import SequenceReplay, check_sequence_draw
+        from .steplog import check_nstep
+        nstep = check_nstep(nstep)
+        forward = check_sequence_draw(length, min_length)
+        if self.steplog is None:
+            raise ValueError("sequence_batch needs a step log (AtariEnvArgs.step_log = True, history_len > 0)")
+        if "forward" in sampler_kw:
+            raise ValueError("sequence_batch sets the sampler's forward itself: pass min_length")
+        if prioritized:
+            sampler = self._per = self.prioritized_sampler(forward=forward, **sampler_kw)
+        else:
+            sampler = self.replay_sampler(forward=forward, **sampler_kw)
+        out = SequenceReplay(self.steplog).batch(sampler, B, length, nstep, gamma, planes, time_major)
+        words = out.pop("payload").view(torch.int32)
+        out["motor_action"] = words[..., 0].contiguous()
+        if self.kind == "fixed":
+            out["sensory_action"] = words[..., 1:3].contiguous().view(torch.float32)
+        if prioritized:
+            out["weight"], out["priority"] = sampler.importance(beta), sampler.weight
+        return out
+
     def update_priorities(self, batch: dict, td_error: torch.Tensor, alpha: float = 0.6, eps: float = 1e-6, **sampler_kw):
         """Write priority = (|td_error| + eps) ** alpha for the rows of a ``replay_batch(..., prioritized=True)`` batch; rows with
         ok = 0 are skipped, and so are rows evicted since the draw.  The table is that of the sampler the last prioritized

@@ -1286,3 +1286,4 @@ int agx_step_flexible_packed(agx_ctx *ctx, const uint8_t *d_screens, int screens
 #include "agx_steplog_impl.h"
 #include "agx_priority_impl.h"
 #include "agx_augment_impl.h"
+#include "agx_sequence_impl.h"

@@ -14,6 +14,7 @@
 //   k_steplog_record / k_steplog_gather  K8  step log: reward / flags / payload rows, n-step returns of drawn samples
 //   k_priority_weights / _chunks / _scan / _draw / _update / _lookup  K9  prioritized sampler: draw proportionally to a priority
 //   k_history_observe_shifted / k_shift_draw  K10  random-shift augmentation: a retained observation moved by a drawn shift
+//   k_sequence_gather / k_sequence_observe  K11  sequence replay: L consecutive steps of one episode per sample, padded with zeros
 //
 // Persistent per-env state (owned by the context, see agx_api.hip):
 //   ring  u8 [N][fs][oh][ow]   numerators k of the reference's float32 k/255 frames
@@ -32,6 +33,7 @@
 #include "agx_k8_steplog.h"
 #include "agx_k9_priority.h"
 #include "agx_k10_augment.h"
+#include "agx_k11_sequence.h"
 #include "agx_k34_resample.h"
 #include "agx_k3_per3.h"
 #include "agx_k4_flex3.h"
