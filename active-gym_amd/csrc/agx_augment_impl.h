@@ -83,9 +83,9 @@ int agx_history_observe_shifted(agx_history *h, int what, const int32_t *d_env, 
                                 int action_dtype, int32_t pad, const int32_t *d_shift, float *d_obs, int32_t *d_fov_loc, uint8_t *d_valid,
                                 void *stream) {
     agx_ctx *ctx = h ? h->ctx : nullptr;          // (the argument checks need no history: they come first)
-    if (what != AGX_HIST_FOVEA && what != AGX_HIST_FULL)
-        return fail(ctx, AGX_E_INVALID, "agx_history_observe_shifted: what must be AGX_HIST_FOVEA or AGX_HIST_FULL, got %d", what);
-    if (pad < 0 || pad > AGX_SHIFT_PAD_LIMIT) return shift_bad_pad(ctx, "agx_history_observe_shifted", pad);
+    const char *who = "agx_history_observe_shifted";
+    if (int rc = hist_bad_what(ctx, who, what)) return rc;
+    if (pad < 0 || pad > AGX_SHIFT_PAD_LIMIT) return shift_bad_pad(ctx, who, pad);
     if (B < 0) return fail(ctx, AGX_E_INVALID, "agx_history_observe_shifted: B = %d", B);
     if (B > 0) {
         if (!d_env) return fail(ctx, AGX_E_INVALID, "agx_history_observe_shifted: null d_env");
@@ -96,51 +96,16 @@ int agx_history_observe_shifted(agx_history *h, int what, const int32_t *d_env, 
     int rc = check_dt(ctx, d_action, action_dtype);
     if (rc) return rc;
     if (!h) return fail(ctx, AGX_E_INVALID, "agx_history_observe_shifted: null h");
-    const agx_config &c = ctx->cfg;
-    if (what == AGX_HIST_FOVEA && c.kind != AGX_KIND_FIXED)
-        return fail(ctx, AGX_E_STATE, "agx_history_observe_shifted: AGX_HIST_FOVEA on a context without a fovea (a base context takes AGX_HIST_FULL only)");
+    if (int rc2 = hist_no_fovea(ctx, who, what)) return rc2;
     if (B == 0) return AGX_OK;                    // (before the range check, as in agx_history_observe)
-    if (!full_range(ctx)) return hist_refuse_range(h, "agx_history_observe_shifted");
-    DeviceGuard g(c.device);
-    const bool fixed = c.kind == AGX_KIND_FIXED;
-    FovParams p = fov_params(ctx, fixed ? d_action : nullptr, action_dtype, nullptr, nullptr, d_obs, fixed ? d_fov_loc : nullptr, nullptr);
-    p.relative = 0;            // a read-time action is absolute whatever the context's action mode
-    p.ring = nullptr;
-    p.head = nullptr;
-    p.loc_in = p.loc_out = nullptr;
-    agx::HistObsParams q;
-    q.h = h->p;
-    q.has_loc = fixed ? 1 : 0;
-    agx::ShiftObsParams sh;
-    sh.pad = pad;
-    const bool fovea = what == AGX_HIST_FOVEA;
-    const size_t lds = fovea ? ctx->plan.lds : 0;
-    const size_t row_bytes = obs_row_bytes(ctx, fovea && c.out_mode == AGX_OUT_RAW);
-    // the sample index rides on gridDim.y: launches of at most 65535 samples, every per-sample array advanced with them
-    for (int32_t at = 0; at < B; at += 65535) {
-        const int nb = std::min<int32_t>(B - at, 65535);
-        FovParams pp = p;
-        pp.obs = reinterpret_cast<float *>(reinterpret_cast<char *>(d_obs) + (size_t)at * row_bytes);
-        if (pp.action) pp.action = static_cast<const char *>(pp.action) + (size_t)at * action_stride(action_dtype);
-        if (pp.user_loc) pp.user_loc += 2 * (size_t)at;
-        q.env = d_env + at;
-        q.index = d_index + at;
-        q.valid = d_valid ? d_valid + at : nullptr;
-        sh.shift = d_shift + 2 * (size_t)at;
-        const dim3 grid(c.frame_stack, nb), block(kThreads);
-        with_obs_type(ctx->obs_type, [&](auto tag) {
-            return with_geom(ctx->plan.headline, geom_r(c), [&](auto g) {
-                auto launch = [&](auto mode) {
-                    hipLaunchKernelGGL((agx::k_history_observe_shifted<decltype(g), decltype(mode)::value, decltype(tag)>), grid, block, lds, S(stream), g, pp,
-                                       q, sh);
-                    return 0;
-                };
-                return fovea ? with_mode(c.out_mode, launch) : launch(std::integral_constant<int, agx::kHistFull>{});
-            });
-        });
-    }
-    AGX_HIP(ctx, hipGetLastError());
-    return AGX_OK;
+    if (!full_range(ctx)) return hist_refuse_range(h, who);
+    DeviceGuard g(ctx->cfg.device);
+    return launch_hist_observe(h, what, d_env, d_index, B, d_action, action_dtype, d_obs, d_fov_loc, d_valid, stream,
+                               [&](auto tag, auto g, auto mode, const HistLaunch &L, const FovParams &pp, const agx::HistObsParams &q) {
+                                   const agx::ShiftObsParams sh{d_shift + 2 * (size_t)L.at, pad};
+                                   hipLaunchKernelGGL((agx::k_history_observe_shifted<decltype(g), decltype(mode)::value, decltype(tag)>), L.grid,
+                                                      dim3(kThreads), L.lds, L.stream, g, pp, q, sh);
+                               });
 }
 
 }  // extern "C"

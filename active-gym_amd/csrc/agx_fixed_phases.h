@@ -1,7 +1,8 @@
 // agx_fixed_phases.h - the phases of the fixed fovea, each stated once: the LDS carve, the window and ytab staging, the
-// raw-crop and mask-out writes, the horizontal pass (phase C) and the vertical lerp (phase D).  K2 (agx_k2_fixed.h) runs them
-// on a ring slot, K5 (agx_k5_history.h) and K6 (agx_k6_glimpse.h) on rows of the frame history: the same arithmetic on the same
-// bytes, so what K5 / K6 write is bit for bit what K2 wrote.
+// raw-crop and mask-out writes, the horizontal pass (phase C) and the vertical lerp (phase D), and the shift policy the tap
+// lookups take.  K2 (agx_k2_fixed.h) runs them on a ring slot; the history readers' plane body (agx_hist_plane.h: K5, K10, K11)
+// and K6 (agx_k6_glimpse.h) on rows of the frame history: the same arithmetic on the same bytes, so what they write is bit for
+// bit what K2 wrote.
 #pragma once
 #include "agx_common.h"
 #include "agx_glimpse.h"
@@ -49,10 +50,28 @@ __device__ __forceinline__ void window_tail(unsigned char *raw, const uint32_t *
     for (int i = tid + kWinRegs * kThreads; i < wwords; i += kThreads) reinterpret_cast<uint32_t *>(raw)[i] = window_word<COHERENT>(wsrc + i, zero);
 }
 
-// ---- ytab staging: yt0 = this thread's row tap {lo, aux, a, b}, already in a register (ytab[min(tid, oh - 1)])
-__device__ __forceinline__ void ytab_stage(Tap *ytab_s, const int4 &yt0, const Tap *ytab, int oh, int tid) {
+// ---- the shift policy of a plane, a compile-time choice.  NoShift (K2, K5, K6, K11) is empty: row(y, n) and col(x, n) are y and
+// x, and nothing of a shift is left in the code.  PlaneShift (K10): output row y of an axis of n rows takes source row
+// shift_src(y, dy, pad, n), output column x source column shift_src(x, dx, pad, n) - in RESIZE a move of whole H columns (the tap
+// of the source column) and of whole output rows (the row tap of the source row), so the arithmetic of phase C / D and its bits
+// are unchanged.
+struct NoShift {
+    static constexpr bool shifted = false;
+    __device__ __forceinline__ int row(int y, int) const { return y; }
+    __device__ __forceinline__ int col(int x, int) const { return x; }
+};
+struct PlaneShift {
+    static constexpr bool shifted = true;
+    int dy, dx, pad;                                       // dy, dx in 0 .. 2 * pad
+    __device__ __forceinline__ int row(int y, int n) const { return shift_src(y, dy, pad, n); }
+    __device__ __forceinline__ int col(int x, int n) const { return shift_src(x, dx, pad, n); }
+};
+
+// ---- ytab staging: yt0 = this thread's row tap {lo, aux, a, b}, already in a register (ytab[sh.row(min(tid, oh - 1), oh)])
+template <class SHIFT = NoShift>
+__device__ __forceinline__ void ytab_stage(Tap *ytab_s, const int4 &yt0, const Tap *ytab, int oh, int tid, const SHIFT &sh = {}) {
     if (tid < oh) *reinterpret_cast<int4 *>(ytab_s + tid) = yt0;
-    for (int i = tid + kThreads; i < oh; i += kThreads) ytab_s[i] = ytab[i];
+    for (int i = tid + kThreads; i < oh; i += kThreads) ytab_s[i] = ytab[sh.row(i, oh)];
 }
 
 // ---- the raw crop [fh][fw] of the window at `win` (row pitch ow)
@@ -86,9 +105,10 @@ __device__ __forceinline__ void mask_out_write(const ObsOut<OT> &oout, const uns
 }
 
 // ---- RESIZE, phase C: H[fh][ow] = horizontal lerp of the window rows.  A thread owns column xcol = tid % ow (its taps xt =
-// xtab[xcol] in registers), rows yb = tid / ow, yb + rstep, ...
+// xtab[sh.col(xcol, ow)] in registers), rows yb = tid / ow, yb + rstep, ...
+template <class SHIFT = NoShift>
 __device__ __forceinline__ void phase_c(float *H, const unsigned char *win, const int4 &xt, const Tap *xtab, int ow, int fh, int xcol,
-                                        int yb, int tid) {
+                                        int yb, int tid, const SHIFT &sh = {}) {
     const int rstep = kThreads / ow;                                  // 3 for ow = 84
     if (rstep > 0) {
         if (yb < rstep) {
@@ -103,29 +123,9 @@ __device__ __forceinline__ void phase_c(float *H, const unsigned char *win, cons
     } else {                                                          // ow > 256: generic striding
         for (int i = tid; i < fh * ow; i += kThreads) {
             const int y = i / ow, x = i - y * ow;
-            const Tap t = xtab[x];
+            const Tap t = xtab[sh.col(x, ow)];
             H[i] = fmaf(t.b, unit_fast((float)win[y * ow + t.aux]), t.a * unit_fast((float)win[y * ow + t.lo]));
         }
-    }
-}
-
-// ---- the shifted siblings (agx_k10_augment.h): output row y takes the row tap of source row shift_src(y, dy, pad, oh), output
-// column x the column tap of source column shift_src(x, dx, pad, ow) - a move of whole H columns and whole output rows, so the
-// arithmetic of phase C / D and its bits are unchanged.  yt0 = ytab[shift_src(min(tid, oh - 1), ..)], xt = xtab[shift_src(xcol, ..)].
-__device__ __forceinline__ void ytab_stage_shifted(Tap *ytab_s, const int4 &yt0, const Tap *ytab, int oh, int tid, int dy, int pad) {
-    if (tid < oh) *reinterpret_cast<int4 *>(ytab_s + tid) = yt0;
-    for (int i = tid + kThreads; i < oh; i += kThreads) ytab_s[i] = ytab[shift_src(i, dy, pad, oh)];
-}
-__device__ __forceinline__ void phase_c_shifted(float *H, const unsigned char *win, const int4 &xt, const Tap *xtab, int ow, int fh,
-                                                int xcol, int yb, int tid, int dx, int pad) {
-    if (kThreads / ow > 0) {                                          // the register-tap form: phase_c itself on the shifted xt
-        phase_c(H, win, xt, xtab, ow, fh, xcol, yb, tid);
-        return;
-    }
-    for (int i = tid; i < fh * ow; i += kThreads) {                   // ow > 256: phase_c's striding form on xtab[cx(x)]
-        const int y = i / ow, x = i - y * ow;
-        const Tap t = xtab[shift_src(x, dx, pad, ow)];
-        H[i] = fmaf(t.b, unit_fast((float)win[y * ow + t.aux]), t.a * unit_fast((float)win[y * ow + t.lo]));
     }
 }
 

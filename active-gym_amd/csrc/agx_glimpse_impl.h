@@ -26,39 +26,30 @@ int agx_history_observe_memory(agx_history *h, int32_t glimpses, const int32_t *
     if (B == 0) return AGX_OK;
     if (!d_env || !d_index || !d_obs) return fail(ctx, AGX_E_INVALID, "agx_history_observe_memory: null buffer");
     DeviceGuard g(c.device);
-    FovParams p = fov_params(ctx, nullptr, 0, nullptr, nullptr, d_obs, nullptr, nullptr);
-    p.relative = 0;
-    p.ring = nullptr;
-    p.head = nullptr;
-    p.loc_in = p.loc_out = nullptr;
+    const FovParams p = hist_fov_params(ctx, nullptr, 0, d_obs, nullptr);
     agx::HistMemParams q;
     q.h = h->p;
     q.glimpses = glimpses;
     const size_t row_bytes = obs_row_bytes(ctx, false);
-    // the sample index rides on gridDim.y: launches of at most 65535 samples
-    for (int32_t at = 0; at < B; at += 65535) {
-        const int nb = std::min<int32_t>(B - at, 65535);
+    return hist_chunks(ctx, c.frame_stack, B, lds, stream, [&](const HistLaunch &L) {
         FovParams pp = p;
-        pp.obs = reinterpret_cast<float *>(reinterpret_cast<char *>(d_obs) + (size_t)at * row_bytes);
-        q.env = d_env + at;
-        q.index = d_index + at;
-        q.loc_out = d_fov_loc ? d_fov_loc + 2 * (size_t)at * glimpses : nullptr;
-        q.taken = d_taken ? d_taken + at : nullptr;
-        const dim3 grid(c.frame_stack, nb), block(kThreads);
+        pp.obs = reinterpret_cast<float *>(reinterpret_cast<char *>(d_obs) + (size_t)L.at * row_bytes);
+        q.env = d_env + L.at;
+        q.index = d_index + L.at;
+        q.loc_out = d_fov_loc ? d_fov_loc + 2 * (size_t)L.at * glimpses : nullptr;
+        q.taken = d_taken ? d_taken + L.at : nullptr;
         with_obs_type(ctx->obs_type, [&](auto tag) {
             return with_geom(headline, geom_r(c), [&](auto g) {
                 using G = decltype(g);
                 using OT = decltype(tag);
                 if (c.out_mode == AGX_OUT_MASK)
-                    hipLaunchKernelGGL((agx::k_history_memory<G, AGX_OUT_MASK, OT>), grid, block, lds, S(stream), g, pp, q);
+                    hipLaunchKernelGGL((agx::k_history_memory<G, AGX_OUT_MASK, OT>), L.grid, dim3(kThreads), L.lds, L.stream, g, pp, q);
                 else
-                    hipLaunchKernelGGL((agx::k_history_memory<G, AGX_OUT_RESIZE, OT>), grid, block, lds, S(stream), g, pp, q);
+                    hipLaunchKernelGGL((agx::k_history_memory<G, AGX_OUT_RESIZE, OT>), L.grid, dim3(kThreads), L.lds, L.stream, g, pp, q);
                 return 0;
             });
         });
-    }
-    AGX_HIP(ctx, hipGetLastError());
-    return AGX_OK;
+    });
 }
 
 }  // extern "C"

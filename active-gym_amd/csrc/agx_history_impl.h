@@ -17,6 +17,86 @@ size_t hist_align(size_t b) { return (b + 255) & ~(size_t)255; }
 
 int hist_refuse_range(agx_history *h, const char *who) { return refuse_range(h->ctx, who); }
 
+// ---- what the readers of the history share (observe, observe_shifted, sequence_observe, observe_memory): the two checks of
+// `what` (each entry point calls them where its own header places them), the FovParams, and the launches
+int hist_bad_what(agx_ctx *ctx, const char *who, int what) {
+    if (what != AGX_HIST_FOVEA && what != AGX_HIST_FULL) return fail(ctx, AGX_E_INVALID, "%s: what must be AGX_HIST_FOVEA or AGX_HIST_FULL, got %d", who, what);
+    return AGX_OK;
+}
+int hist_no_fovea(agx_ctx *ctx, const char *who, int what) {
+    if (what == AGX_HIST_FOVEA && ctx->cfg.kind != AGX_KIND_FIXED)
+        return fail(ctx, AGX_E_STATE, "%s: AGX_HIST_FOVEA on a context without a fovea (a base context takes AGX_HIST_FULL only)", who);
+    return AGX_OK;
+}
+
+// K2's parameters for a kernel that reads history rows: no ring, no head, no fov state; a base context takes no action and
+// writes no fov_loc
+FovParams hist_fov_params(agx_ctx *ctx, const void *d_action, int action_dtype, void *d_obs, int32_t *d_fov_loc) {
+    const bool fixed = ctx->cfg.kind == AGX_KIND_FIXED;
+    FovParams p = fov_params(ctx, fixed ? d_action : nullptr, action_dtype, nullptr, nullptr, static_cast<float *>(d_obs), fixed ? d_fov_loc : nullptr, nullptr);
+    p.relative = 0;            // a read-time action is absolute whatever the context's action mode
+    p.ring = nullptr;
+    p.head = nullptr;
+    p.loc_in = p.loc_out = nullptr;
+    return p;
+}
+
+// One launch of a history reader: rows [at, at + grid.y) of the call ride on gridDim.y, at most 65535 of them.
+struct HistLaunch {
+    int64_t at;
+    dim3 grid;
+    size_t lds;
+    hipStream_t stream;
+};
+constexpr int64_t kHistRowsPerLaunch = 65535;
+template <class F>
+int hist_chunks(agx_ctx *ctx, int grid_x, int64_t rows, size_t lds, void *stream, F &&fn) {
+    for (int64_t at = 0; at < rows; at += kHistRowsPerLaunch)
+        fn(HistLaunch{at, dim3(grid_x, (unsigned)std::min<int64_t>(rows - at, kHistRowsPerLaunch)), lds, S(stream)});
+    AGX_HIP(ctx, hipGetLastError());
+    return AGX_OK;
+}
+// ... of one that writes planes by agx_hist_plane.h: fn(tag, g, mode, L) launches its kernel <decltype(g), mode, decltype(tag)>
+// for the context's observation type and geometry and the mode `what` asks for, with its own per-row pointers advanced to L.at
+template <class F>
+int launch_hist_planes(agx_ctx *ctx, int what, int grid_x, int64_t rows, void *stream, F &&fn) {
+    const agx_config &c = ctx->cfg;
+    const bool fovea = what == AGX_HIST_FOVEA;
+    return hist_chunks(ctx, grid_x, rows, fovea ? ctx->plan.lds : 0, stream, [&](const HistLaunch &L) {
+        with_obs_type(ctx->obs_type, [&](auto tag) {
+            return with_geom(ctx->plan.headline, geom_r(c), [&](auto g) {
+                auto launch = [&](auto mode) {
+                    fn(tag, g, mode, L);
+                    return 0;
+                };
+                return fovea ? with_mode(c.out_mode, launch) : launch(std::integral_constant<int, agx::kHistFull>{});
+            });
+        });
+    });
+}
+// ... and of one on grid (fs, B) over a call's per-sample arrays (observe and its shifted form): fn(tag, g, mode, L, p, q)
+template <class F>
+int launch_hist_observe(agx_history *h, int what, const int32_t *d_env, const int64_t *d_index, int32_t B, const void *d_action, int action_dtype,
+                        float *d_obs, int32_t *d_fov_loc, uint8_t *d_valid, void *stream, F &&fn) {
+    agx_ctx *ctx = h->ctx;
+    const agx_config &c = ctx->cfg;
+    const FovParams p = hist_fov_params(ctx, d_action, action_dtype, d_obs, d_fov_loc);
+    agx::HistObsParams q;
+    q.h = h->p;
+    q.has_loc = c.kind == AGX_KIND_FIXED ? 1 : 0;
+    const size_t row_bytes = obs_row_bytes(ctx, what == AGX_HIST_FOVEA && c.out_mode == AGX_OUT_RAW);
+    return launch_hist_planes(ctx, what, c.frame_stack, B, stream, [&](auto tag, auto g, auto mode, const HistLaunch &L) {
+        FovParams pp = p;
+        pp.obs = reinterpret_cast<float *>(reinterpret_cast<char *>(d_obs) + (size_t)L.at * row_bytes);
+        if (pp.action) pp.action = static_cast<const char *>(pp.action) + (size_t)L.at * action_stride(action_dtype);
+        if (pp.user_loc) pp.user_loc += 2 * (size_t)L.at;
+        q.env = d_env + L.at;
+        q.index = d_index + L.at;
+        q.valid = d_valid ? d_valid + L.at : nullptr;
+        fn(tag, g, mode, L, pp, q);
+    });
+}
+
 }  // namespace
 
 extern "C" {
@@ -126,51 +206,21 @@ int agx_history_observe(agx_history *h, int what, const int32_t *d_env, const in
     if (!h) return AGX_E_INVALID;
     agx_ctx *ctx = h->ctx;
     const agx_config &c = ctx->cfg;
-    if (what != AGX_HIST_FOVEA && what != AGX_HIST_FULL) return fail(ctx, AGX_E_INVALID, "agx_history_observe: what must be AGX_HIST_FOVEA or AGX_HIST_FULL, got %d", what);
-    if (what == AGX_HIST_FOVEA && c.kind != AGX_KIND_FIXED)
-        return fail(ctx, AGX_E_STATE, "agx_history_observe: AGX_HIST_FOVEA on a context without a fovea (a base context takes AGX_HIST_FULL only)");
+    const char *who = "agx_history_observe";
+    if (int rc = hist_bad_what(ctx, who, what)) return rc;
+    if (int rc = hist_no_fovea(ctx, who, what)) return rc;
     if (B < 0) return fail(ctx, AGX_E_INVALID, "agx_history_observe: B = %d", B);
     if (B == 0) return AGX_OK;
     if (!d_env || !d_index || !d_obs) return fail(ctx, AGX_E_INVALID, "agx_history_observe: null buffer");
     int rc = check_dt(ctx, d_action, action_dtype);
     if (rc) return rc;
-    if (!full_range(ctx)) return hist_refuse_range(h, "agx_history_observe");
+    if (!full_range(ctx)) return hist_refuse_range(h, who);
     DeviceGuard g(c.device);
-    const bool fixed = c.kind == AGX_KIND_FIXED;
-    FovParams p = fov_params(ctx, fixed ? d_action : nullptr, action_dtype, nullptr, nullptr, d_obs, fixed ? d_fov_loc : nullptr, nullptr);
-    p.relative = 0;            // a read-time action is absolute whatever the context's action mode
-    p.ring = nullptr;
-    p.head = nullptr;
-    p.loc_in = p.loc_out = nullptr;
-    agx::HistObsParams q;
-    q.h = h->p;
-    q.has_loc = fixed ? 1 : 0;
-    const bool fovea = what == AGX_HIST_FOVEA;
-    const size_t lds = fovea ? ctx->plan.lds : 0;
-    const size_t row_bytes = obs_row_bytes(ctx, fovea && c.out_mode == AGX_OUT_RAW);
-    // the sample index rides on gridDim.y: launches of at most 65535 samples
-    for (int32_t at = 0; at < B; at += 65535) {
-        const int nb = std::min<int32_t>(B - at, 65535);
-        FovParams pp = p;
-        pp.obs = reinterpret_cast<float *>(reinterpret_cast<char *>(d_obs) + (size_t)at * row_bytes);
-        if (pp.action) pp.action = static_cast<const char *>(pp.action) + (size_t)at * action_stride(action_dtype);
-        if (pp.user_loc) pp.user_loc += 2 * (size_t)at;
-        q.env = d_env + at;
-        q.index = d_index + at;
-        q.valid = d_valid ? d_valid + at : nullptr;
-        const dim3 grid(c.frame_stack, nb), block(kThreads);
-        with_obs_type(ctx->obs_type, [&](auto tag) {
-            return with_geom(ctx->plan.headline, geom_r(c), [&](auto g) {
-                auto launch = [&](auto mode) {
-                    hipLaunchKernelGGL((agx::k_history_observe<decltype(g), decltype(mode)::value, decltype(tag)>), grid, block, lds, S(stream), g, pp, q);
-                    return 0;
-                };
-                return fovea ? with_mode(c.out_mode, launch) : launch(std::integral_constant<int, agx::kHistFull>{});
-            });
-        });
-    }
-    AGX_HIP(ctx, hipGetLastError());
-    return AGX_OK;
+    return launch_hist_observe(h, what, d_env, d_index, B, d_action, action_dtype, d_obs, d_fov_loc, d_valid, stream,
+                               [&](auto tag, auto g, auto mode, const HistLaunch &L, const FovParams &pp, const agx::HistObsParams &q) {
+                                   hipLaunchKernelGGL((agx::k_history_observe<decltype(g), decltype(mode)::value, decltype(tag)>), L.grid,
+                                                      dim3(kThreads), L.lds, L.stream, g, pp, q);
+                               });
 }
 
 int agx_loop_set_history(agx_loop *l, agx_history *h) {

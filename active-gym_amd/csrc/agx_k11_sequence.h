@@ -1,7 +1,7 @@
 // agx_k11_sequence.h - K11: sequence replay on the frame history (include/agx_sequence.h).  k_sequence_gather finds where each
 // sequence ends and runs the step log's walk for every live step, k_sequence_observe re-creates the observation planes of every
 // step and writes zeros for the padded ones.  The length rule is agx_sequence_math.h's, the walk agx_steplog_fold.h's, the
-// observation phases agx_fixed_phases.h's: nothing is restated here.  Every device write is an ordinary vector store.
+// observation plane agx_hist_plane.h's: nothing is restated here.  Every device write is an ordinary vector store.
 #pragma once
 #include "agx_k5_history.h"
 #include "agx_k8_steplog.h"
@@ -102,11 +102,10 @@ __global__ __launch_bounds__(kThreads) void k_sequence_gather(StepLogParams p, S
 // k_sequence_observe<G, MODE, OT>: grid = (planes, rows of this launch), block = 256.  Workgroup (pl, y) owns plane pl - stack
 // position j = fs - planes + pl - of output row row0 + y, which is step (b, l) of the call's layout.  b, l, the start index and
 // d_len[b] are workgroup-uniform and come through the scalar cache.  The step is live iff l < min(len, L) and (n, k + l) is
-// valid by k_history_observe's own rule, re-checked here whatever d_len says.  A live plane is k_history_observe's plane j of
-// sample (n, k + l) at the recorded fov_loc: the same sample resolution, age rule, zero-frame path, FixedCarve, phases and
-// stores.  Every other plane is written as literal zeros through the same stores (store_obs / store_packed), not through the
-// phases on a zero window: the contract is all-zero BYTES, and it holds whatever the signs of a context's taps.
-// MODE = kHistFull: the full-frame k/255 write.
+// valid by the history's rule (hist_resolve), re-checked here whatever d_len says.  A live plane is plane j of sample (n, k + l)
+// at the recorded fov_loc, by the history readers' shared body (agx_hist_plane.h) with no action and no shift.  Every other
+// plane is written as literal zeros through the same stores (store_obs / store_packed), not through the phases on a zero
+// window: the contract is all-zero BYTES, and it holds whatever the signs of a context's taps.
 // ---------------------------------------------------------------------------------------------
 struct SeqObsParams {
     HistParams h;
@@ -123,9 +122,7 @@ template <class G, int MODE, class OT>
 __global__ __launch_bounds__(kThreads) void k_sequence_observe(G g, FovParams p, SeqObsParams q) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int pl = blockIdx.x, tid = threadIdx.x;
-    const int oh = g.oh(), ow = g.ow(), fh = g.fh(), fw = g.fw();
-    const int T = q.h.T, N = q.h.N, fs = q.h.fs;
-    const int ow4 = ow >> 2;
+    const bool first = pl == 0 && tid == 0;
     // ---- the step this row is
     const int row = q.row0 + (int)blockIdx.y;
     int b, l;
@@ -139,95 +136,32 @@ __global__ __launch_bounds__(kThreads) void k_sequence_observe(G g, FovParams p,
     const int n = uniform_load_i32(q.env + b);
     const int64_t k0 = uniform_load_i64(q.index + b);
     const int len = uniform_load_i32(q.len + b);
-    // ---- the sample (n, k0 + l) by the history's rule, and the age of its row
-    bool ok = l < min(len, q.L) && n >= 0 && n < N && k0 >= -(int64_t)kSequenceLimit && k0 <= INT64_MAX - kSequenceLimit;
-    int64_t k = 0;
-    int row_k = 0, age = 0;
-    if (ok) {
-        k = k0 + l;
-        const int64_t cnt = uniform_load_i64(q.h.count + n);
-        ok = steplog_ok0(k, cnt, T);
-        if (ok) {
-            row_k = hist_row(k, T);
-            age = (int)uniform_load_u8(q.h.age + (size_t)row_k * N + n);
-            ok = sequence_start_ok(k, cnt, T, fs, age);
-        }
-    }
-    const bool crop = MODE == AGX_OUT_RAW;
-    const size_t plane = ((size_t)row * q.planes + pl) * (size_t)(crop ? fh * fw : oh * ow);       // in elements
-    if (pl == 0 && tid == 0 && q.live) q.live[row] = ok ? 1 : 0;
-    if (!ok) {
-        if (pl == 0 && tid == 0 && p.user_loc) {
+    // ---- the sample (n, k0 + l) by the history's rule, re-checked here whatever d_len says
+    const bool in_len = l < min(len, q.L) && k0 >= -(int64_t)kSequenceLimit && k0 <= INT64_MAX - kSequenceLimit;
+    const HistStack st = in_len ? hist_resolve(q.h, n, k0 + l) : HistStack{false, 0, 0, 0};
+    const int elems = hist_plane_elems<MODE>(g);
+    OT *plane = reinterpret_cast<OT *>(p.obs) + ((size_t)row * q.planes + pl) * (size_t)elems;
+    if (first && q.live) q.live[row] = st.ok ? 1 : 0;
+    if (!st.ok) {
+        if (first && p.user_loc) {
             p.user_loc[2 * (size_t)row] = 0;
             p.user_loc[2 * (size_t)row + 1] = 0;
         }
-        if (crop) {
-            const auto cout = packed_out<OT>(reinterpret_cast<OT *>(p.obs) + plane, fh * fw);
-            for (int i = tid; i < fh * fw; i += kThreads) store_packed(cout, i, 0.0f);
+        if (MODE == AGX_OUT_RAW) {
+            const auto cout = packed_out<OT>(plane, elems);
+            for (int i = tid; i < elems; i += kThreads) store_packed(cout, i, 0.0f);
         } else {
-            const auto oout = obs_out<OT>(reinterpret_cast<obs4_t<OT> *>(reinterpret_cast<OT *>(p.obs) + plane), oh * ow4);
-            for (int i = tid; i < oh * ow4; i += kThreads) store_obs(oout, i, make_float4(0.0f, 0.0f, 0.0f, 0.0f));
+            const int nq = g.oh() * (g.ow() >> 2);
+            const auto oout = obs_out<OT>(reinterpret_cast<obs4_t<OT> *>(plane), nq);
+            for (int i = tid; i < nq; i += kThreads) store_obs(oout, i, make_float4(0.0f, 0.0f, 0.0f, 0.0f));
         }
         return;
     }
-    const int j = fs - q.planes + pl;
-    const int back = fs - 1 - j;
-    const bool zero = back > age;
-    int hrow = row_k - back;                              // back <= fs - 1 < T
-    if (hrow < 0) hrow += T;
-    const int fbytes = oh * ow;
-    const uint32_t *fsrc = reinterpret_cast<const uint32_t *>(q.h.frames + ((size_t)hrow * N + n) * (size_t)fbytes);
-
-    // ---- position: the recorded fov_loc of row k
-    int r = 0, c = 0;
-    int4 xt = make_int4(0, 0, 0, 0);
-    int4 yt0 = make_int4(0, 0, 0, 0);
-    if (MODE == AGX_OUT_RESIZE) {                         // this thread's taps go out first, as in K2
-        xt = *reinterpret_cast<const int4 *>(p.xtab + tid % ow);
-        yt0 = *reinterpret_cast<const int4 *>(p.ytab + min(tid, oh - 1));
-    }
-    if (q.has_loc) {
-        const int2 rc = uniform_load_i32x2(q.h.loc + 2 * ((size_t)row_k * N + n));
-        // a recorded fov_loc is in range unless the caller set one that is not (agx_set_fov_state): the window stays inside the frame
-        r = min(max(rc.x, 0), oh - fh);
-        c = min(max(rc.y, 0), ow - fw);
-        if (pl == 0 && tid == 0 && p.user_loc) {
-            p.user_loc[2 * (size_t)row] = r;
-            p.user_loc[2 * (size_t)row + 1] = c;
-        }
-    }
-    if (MODE == kHistFull) {
-        // the base observation: k_full's arithmetic (unit: the IEEE quotient) and its written-through store
-        const auto oout = obs_out<OT>(reinterpret_cast<obs4_t<OT> *>(reinterpret_cast<OT *>(p.obs) + plane), oh * ow4);
-        for (int i = tid; i < oh * ow4; i += kThreads) store_obs(oout, i, unit4(zero ? 0u : fsrc[i]));
-        return;
-    }
-    const FixedCarve lds = fixed_carve(smem, oh, ow, fh);            // (agx_api.hip: fixed_lds)
-    {
-        const uint32_t *wsrc = fsrc + r * ow4;
-        const int wwords = (fh * ow) >> 2;
-        uint32_t ww[kWinRegs];
-#pragma unroll
-        for (int i = 0; i < kWinRegs; ++i) ww[i] = window_reg(wsrc, i, wwords, tid, zero);
-        if (MODE == AGX_OUT_RESIZE) ytab_stage(lds.ytab_s, yt0, p.ytab, oh, tid);
-        window_land(lds.raw, ww, wwords, tid);
-        window_tail(lds.raw, wsrc, wwords, tid, zero);
-        __syncthreads();
-    }
-    const unsigned char *win = lds.raw + c;
-    if (MODE == AGX_OUT_RAW) {
-        raw_crop_write(reinterpret_cast<OT *>(p.obs) + plane, win, ow, fh, fw, tid);
-        return;
-    }
-    const auto oout = obs_out<OT>(reinterpret_cast<obs4_t<OT> *>(reinterpret_cast<OT *>(p.obs) + plane), oh * ow4);
-    if (MODE == AGX_OUT_MASK) {
-        mask_out_write(oout, lds.raw, r, c, oh, ow, fh, fw, tid);
-        return;
-    }
-    const int xcol = tid % ow, yb = tid / ow;
-    phase_c(lds.H, win, xt, p.xtab, ow, fh, xcol, yb, tid);
-    __syncthreads();
-    phase_d_write(oout, lds.H, lds.ytab_s, oh, ow4, tid);
+    const HistPlaneSrc src = hist_plane_src(g, q.h, st, n, q.h.fs - q.planes + pl);
+    const HistTaps taps = hist_taps<MODE>(p, g.oh(), g.ow(), tid, NoShift{});
+    int r, c;
+    hist_position<false>(p, q.h, q.has_loc, st.row_k, n, 0, g.oh() - g.fh(), g.ow() - g.fw(), first, (size_t)row, r, c);
+    hist_plane_write<G, MODE, OT>(g, p, smem, src, r, c, taps, plane, NoShift{});
 }
 
 }  // namespace agx

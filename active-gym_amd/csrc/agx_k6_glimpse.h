@@ -88,6 +88,7 @@ __global__ __launch_bounds__(kThreads) void k_history_memory(G g, FovParams p, H
             int2 rc;
             uniform_load_age_loc(q.h.age + hrow, q.h.loc + 2 * hrow, age_i, rc);
             if (i == 0) age_k = age_i;
+            // (hist_stack_ok(k - i, cnt, T, fs, age_i) against the loop's own `oldest`: calling it here costs 11 instructions and 3 SGPRs)
             live = i <= age_k && k - i - min(age_i, fs - 1) >= oldest;
             if (live) {
                 nt = i + 1;

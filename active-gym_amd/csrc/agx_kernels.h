@@ -16,6 +16,11 @@
 //   k_history_observe_shifted / k_shift_draw  K10  random-shift augmentation: a retained observation moved by a drawn shift
 //   k_sequence_gather / k_sequence_observe  K11  sequence replay: L consecutive steps of one episode per sample, padded with zeros
 //
+// The fixed fovea's phases are stated once in agx_fixed_phases.h (K2, K5, K6, K10, K11 run them).  The three kernels that re-create
+// observation planes from history rows - k_history_observe, k_history_observe_shifted, k_sequence_observe - are one body,
+// agx_hist_plane.h (sample resolution, source row, position, plane write), under their own indexing and shift policy; the
+// validity rule of a history sample is agx_hist_rule.h's.
+//
 // Persistent per-env state (owned by the context, see agx_api.hip):
 //   ring  u8 [N][fs][oh][ow]   numerators k of the reference's float32 k/255 frames
 //   head  i32[2][N]            next slot to write == oldest frame; double-buffered so that the

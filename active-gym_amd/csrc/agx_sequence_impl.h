@@ -80,8 +80,7 @@ int agx_sequence_observe(agx_history *h, int what, const int32_t *d_env, const i
     agx_ctx *ctx = h ? h->ctx : nullptr;
     const char *who = "agx_sequence_observe";
     if (L < 1 || L > AGX_SEQUENCE_LIMIT) return seq_bad_L(ctx, who, L);
-    if (what != AGX_HIST_FOVEA && what != AGX_HIST_FULL)
-        return fail(ctx, AGX_E_INVALID, "%s: what must be AGX_HIST_FOVEA or AGX_HIST_FULL, got %d", who, what);
+    if (int rc = hist_bad_what(ctx, who, what)) return rc;
     if (planes < 1) return fail(ctx, AGX_E_INVALID, "%s: planes must be >= 1, got %d", who, planes);
     if (int rc = seq_bad_B(ctx, who, B, L)) return rc;
     if (B > 0 && (!d_env || !d_index || !d_len || !d_obs))
@@ -89,17 +88,11 @@ int agx_sequence_observe(agx_history *h, int what, const int32_t *d_env, const i
     if (!h) return fail(ctx, AGX_E_INVALID, "%s: null argument (h)", who);
     const agx_config &c = ctx->cfg;
     if (planes > c.frame_stack) return fail(ctx, AGX_E_INVALID, "%s: planes = %d exceeds frame_stack %d", who, planes, c.frame_stack);
-    if (what == AGX_HIST_FOVEA && c.kind != AGX_KIND_FIXED)
-        return fail(ctx, AGX_E_STATE, "%s: AGX_HIST_FOVEA on a context without a fovea (a base context takes AGX_HIST_FULL only)", who);
+    if (int rc = hist_no_fovea(ctx, who, what)) return rc;
     if (B == 0) return AGX_OK;                    // (before the range check, as in agx_history_observe)
     if (!full_range(ctx)) return hist_refuse_range(h, who);
     DeviceGuard g(c.device);
-    const bool fixed = c.kind == AGX_KIND_FIXED;
-    FovParams p = fov_params(ctx, nullptr, 0, nullptr, nullptr, static_cast<float *>(d_obs), fixed ? d_fov_loc : nullptr, nullptr);
-    p.relative = 0;
-    p.ring = nullptr;
-    p.head = nullptr;
-    p.loc_in = p.loc_out = nullptr;
+    const FovParams p = hist_fov_params(ctx, nullptr, 0, d_obs, d_fov_loc);
     agx::SeqObsParams q;
     q.h = h->p;
     q.env = d_env;
@@ -110,27 +103,12 @@ int agx_sequence_observe(agx_history *h, int what, const int32_t *d_env, const i
     q.L = L;
     q.planes = planes;
     q.time_major = time_major ? 1 : 0;
-    q.has_loc = fixed ? 1 : 0;
-    const bool fovea = what == AGX_HIST_FOVEA;
-    const size_t lds = fovea ? ctx->plan.lds : 0;
-    const int32_t rows = B * L;
-    // the output row rides on gridDim.y: launches of at most 65535 rows, each told its first row
-    for (int64_t at = 0; at < rows; at += 65535) {
-        const int nb = (int)std::min<int64_t>(rows - at, 65535);
-        q.row0 = (int32_t)at;
-        const dim3 grid(planes, nb), block(kThreads);
-        with_obs_type(ctx->obs_type, [&](auto tag) {
-            return with_geom(ctx->plan.headline, geom_r(c), [&](auto g) {
-                auto launch = [&](auto mode) {
-                    hipLaunchKernelGGL((agx::k_sequence_observe<decltype(g), decltype(mode)::value, decltype(tag)>), grid, block, lds, S(stream), g, p, q);
-                    return 0;
-                };
-                return fovea ? with_mode(c.out_mode, launch) : launch(std::integral_constant<int, agx::kHistFull>{});
-            });
-        });
-    }
-    AGX_HIP(ctx, hipGetLastError());
-    return AGX_OK;
+    q.has_loc = c.kind == AGX_KIND_FIXED ? 1 : 0;
+    // the output row rides on gridDim.y: each launch is told its first row, and the kernel places its own outputs
+    return launch_hist_planes(ctx, what, planes, (int64_t)B * L, stream, [&](auto tag, auto g, auto mode, const HistLaunch &ln) {
+        q.row0 = (int32_t)ln.at;
+        hipLaunchKernelGGL((agx::k_sequence_observe<decltype(g), decltype(mode)::value, decltype(tag)>), ln.grid, dim3(kThreads), ln.lds, ln.stream, g, p, q);
+    });
 }
 
 }  // extern "C"

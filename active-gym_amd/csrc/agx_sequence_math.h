@@ -9,11 +9,10 @@ namespace agx {
 
 constexpr int32_t kSequenceLimit = 256;      // AGX_SEQUENCE_LIMIT
 
-// (n, k) is valid by the history's own rule: retained, and so is the oldest row its stack needs.  age_k = the age byte of row k,
-// read only where steplog_ok0(k, cnt, T) holds; cnt = count[n].
+// (n, k) is valid by the history's own rule (agx_hist_rule.h): retained, and so is the oldest row its stack needs.  age_k = the
+// age byte of row k, read only where steplog_ok0(k, cnt, T) holds; cnt = count[n].
 AGX_HD bool sequence_start_ok(int64_t k, int64_t cnt, int32_t T, int32_t fs, int32_t age_k) {
-    const int64_t first = k - (age_k < fs - 1 ? age_k : fs - 1);
-    return first >= 0 && first >= cnt - T;
+    return hist_stack_ok(k, cnt, T, fs, age_k);
 }
 
 // Row j > k ends the sequence in front of it: the end of the history, or the first append of another episode.  rows.at(j) places

@@ -2,18 +2,7 @@
 // __host__ __device__ functions over an accessor argument: k_steplog_gather (agx_k8_steplog.h) and a plain C++ program
 // (tests/steplog_harness.cpp) run the very same code.  Nothing here touches the GPU.
 #pragma once
-#include <stdint.h>
-
-#if defined(__HIPCC__)
-#include <hip/hip_runtime.h>
-#endif
-#ifndef AGX_HD
-#if defined(__HIPCC__)
-#define AGX_HD __host__ __device__ inline
-#else
-#define AGX_HD inline
-#endif
-#endif
+#include "agx_hist_rule.h"
 
 namespace agx {
 
@@ -43,7 +32,7 @@ struct StepFold {
 };
 
 // ok0: n is an env and row k is still retained (cnt = count[n], read only when n is an env)
-AGX_HD bool steplog_ok0(int64_t k, int64_t cnt, int32_t T) { return k >= 0 && k < cnt && k >= cnt - T; }
+AGX_HD bool steplog_ok0(int64_t k, int64_t cnt, int32_t T) { return hist_retained(k, cnt, T); }
 
 // Step i (1 first) of the walk from k.  r = rows.at(j) places row j of the sample's env (j mod T, once per step); rows.age(r),
 // rows.stamp(r), rows.reward(r), rows.flags(r) read it.  They are called for retained j only, and reward / flags only behind a

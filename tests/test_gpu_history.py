@@ -163,6 +163,58 @@ def test_generic_geometry(obs, fov, fs, mode):
     pipe.close()
 
 
+@pytest.mark.parametrize("kind, obs, fov, mode, dtype", [
+    ("fixed", (8, 264), (4, 100), "resize", torch.float32),        # ow > 256: the striding phase C
+    ("fixed", (40, 160), (24, 50), "resize", torch.float32),       # 960 window dwords > 3 x 256: window_tail runs
+    ("fixed", (40, 160), (24, 50), "mask", torch.float32),
+    ("fixed", (10, 12), (3, 5), "raw", torch.float32),             # oh * ow / 4 far below one pass
+    ("base", (10, 12), (3, 5), "full", torch.float32),
+    ("fixed", (84, 84), (30, 30), "resize", torch.float32),        # the compile-time geometry
+    ("fixed", (84, 84), (30, 30), "resize", torch.bfloat16),
+], ids=lambda v: "x".join(map(str, v)) if isinstance(v, tuple) else str(v).replace("torch.", ""))
+def test_three_readers_write_the_same_plane(kind, obs, fov, mode, dtype):
+    """FrameHistory.observe, RandomShift(pad=0).observe and SequenceReplay.observe(L = 1, planes = fs) of every sample of the model,
+    valid or not: bit-equal observation, fov_loc and valid / live byte on the valid rows.  Invalid rows keep the sentinel on the
+    observe side and are zeros, fov_loc (0, 0), on the sequence side."""
+    from active_gym import FrameHistory, RandomShift, SequenceReplay, StepLog
+    from test_gpu_augment import _tensors
+    fs, what = 3, "full" if mode == "full" else "fovea"
+    pipe = _pipe(4, kind=kind, obs=obs, fov=fov, fs=fs, mode=mode, action_mode="relative", dtype=dtype)
+    hist = FrameHistory(pipe, 5)
+    model, rec = _run(pipe, hist, commands(11, 4, 9), 11)
+    samples = _samples(model)
+    issued, nvalid, _, evicted = _kinds(model, rec, samples)
+    assert nvalid >= 8 and evicted >= 1
+    env, idx = _tensors(samples)
+    B, bits = len(samples), BITS[dtype]
+    shape = (B,) + hist.obs_row_shape(what)
+    aug, seq = RandomShift(hist, pad=0), SequenceReplay(StepLog(hist, 0))
+    reads = []
+    for read, kw in ((hist.observe, {}), (aug.observe, {"shift": torch.zeros((B, 2), dtype=torch.int32, device=DEV)})):
+        out = torch.full(shape, SENTINEL, dtype=dtype, device=DEV)
+        loc = torch.full((B, 2), -77, dtype=torch.int32, device=DEV)
+        reads.append(read(env, idx, what=what, out=out, loc_out=loc, **kw))
+    (obs_h, loc_h, valid_h), (obs_a, loc_a, valid_a) = reads
+    out = torch.full((B, 1) + shape[1:], SENTINEL, dtype=dtype, device=DEV)
+    loc = torch.full((B, 1, 2), -77, dtype=torch.int32, device=DEV)
+    obs_s, loc_s, live = seq.observe(env, idx, seq.lengths(env, idx, 1), 1, what=what, planes=fs, out=out, loc_out=loc)
+    obs_s, loc_s, live = obs_s[:, 0], loc_s[:, 0], live[:, 0]
+    v = valid_h.bool()
+    assert np.array_equal(v.cpu().numpy(), np.array([model.valid(n, k) for n, k in samples])) and int(v.sum()) == nvalid
+    assert torch.equal(valid_a, valid_h) and torch.equal(live, valid_h), "the valid / live bytes differ"
+    # the observe side, whole: equal on the valid rows, the sentinel on both elsewhere
+    assert torch.equal(obs_a.view(bits), obs_h.view(bits)) and torch.equal(loc_a, loc_h)
+    assert torch.equal(obs_h[~v].view(bits), torch.full_like(obs_h[~v], SENTINEL).view(bits)) and bool((loc_h[~v] == -77).all())
+    assert torch.equal(obs_s[v].view(bits), obs_h[v].view(bits)), "sequence observe differs from observe on a valid row"
+    assert not bool(obs_s[~v].view(bits).any()), "a dead step is not all-zero bytes"
+    if kind == "fixed":
+        assert torch.equal(loc_s[v], loc_h[v]) and not bool(loc_s[~v].any())
+    for b in torch.nonzero(v).flatten().tolist():              # ... and all three are what the step wrote
+        o, l, f = rec[samples[b]]
+        assert torch.equal(obs_h[b].view(bits), (o if f is None else f).view(bits)), samples[b]
+    pipe.close()
+
+
 @pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16], ids=["bf16", "f16"])
 @pytest.mark.parametrize("mode", ["resize", "raw", "mask"])
 def test_16_bit_outputs(mode, dtype):
