@@ -20,7 +20,8 @@ struct FixedCarve {
     Tap *ytab_s;
     float *H;
 };
-__device__ __forceinline__ FixedCarve fixed_carve(unsigned char *raw, int oh, int ow, int fh, int windows = 1) {
+// (host too: tests/host_tables_harness.cpp holds K6's region ends against agx_plan.h's memory_lds)
+__host__ __device__ __forceinline__ FixedCarve fixed_carve(unsigned char *raw, int oh, int ow, int fh, int windows = 1) {
     Tap *ytab_s = reinterpret_cast<Tap *>(raw + windows * fixed_pad(fh, ow));
     return {raw, ytab_s, reinterpret_cast<float *>(ytab_s + oh)};
 }

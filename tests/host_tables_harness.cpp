@@ -13,6 +13,7 @@
 //        harness k1plan obs [knob=1 ...]        which K1 ingest form each screen layout selects at obs x obs, and what it branches on
 //        knob: generic flex_v2 per_v2 no_full - the context's fallback knobs (agx_plan.h: Knobs); none given = none set
 //        harness k1tables obs                   the K1 tables of build_k1: x0 x1 a0 a1 y0 y1 b0 b1 and the source-row list
+//        harness carve oh ow fh fw resize|mask  k_history_memory's LDS regions (fixed_carve) against memory_lds, P = 1, 3, 8
 #include <cstdio>
 #include <cstdlib>
 #include <random>
@@ -336,7 +337,55 @@ static int k1tables_main(int argc, char **argv) {
     return 0;
 }
 
+// ---- K6 (agx_k6_glimpse.h): the LDS regions k_history_memory touches, from fixed_carve(smem + kMemTableBytes, oh, ow, fh, P) -
+// the call the kernel makes - against what memory_lds (agx_plan.h) hands the launch as dynamic LDS:
+//   table int2[AGX_GLIMPSE_LIMIT] | raw .. raw + P * fixed_pad | RESIZE: ytab_s .. + oh | H .. + 2 * fh * ow | GeomR: acc .. + oh * ow
+// One line per P = 1, 3, 8: "P=p end=<bytes> lds=<memory_lds> aligned=<0|1> headline=<0|1>"; exit status 1 if a region ends behind
+// memory_lds or one that the kernel reads as float4 / int4 (window dwords as uint32_t, the table as int2) is misaligned.
+static int carve_main(int argc, char **argv) {
+    if (argc < 7) return 2;
+    agx_config c{};
+    c.kind = AGX_KIND_FIXED;
+    c.obs_h = atoi(argv[2]); c.obs_w = atoi(argv[3]); c.fov_h = atoi(argv[4]); c.fov_w = atoi(argv[5]);
+    c.out_mode = !strcmp(argv[6], "resize") ? AGX_OUT_RESIZE : !strcmp(argv[6], "mask") ? AGX_OUT_MASK : -1;
+    if (c.out_mode < 0 || c.obs_h < 1 || c.obs_w < 4 || (c.obs_w & 3) || c.fov_h < 1 || c.fov_h > c.obs_h) return 2;
+    const int oh = c.obs_h, ow = c.obs_w, fh = c.fov_h;
+    const bool headline = headline_fixed(c);
+    // (a real buffer, so that the carve's pointer arithmetic stays inside one object: 8 windows of the largest geometry fit)
+    static std::vector<unsigned char> store;
+    store.assign((size_t)kMemTableBytes + AGX_GLIMPSE_LIMIT * (size_t)fixed_pad(fh, ow) + (size_t)oh * sizeof(Tap) +
+                     (2 * (size_t)fh * ow + (size_t)oh * ow) * sizeof(float) + 64, 0);
+    unsigned char *smem = store.data() + ((16 - reinterpret_cast<uintptr_t>(store.data()) % 16) % 16);      // as the kernel's: 16-B aligned
+    int bad = 0;
+    for (int P : {1, 3, 8}) {
+        const FixedCarve lds = fixed_carve(smem + kMemTableBytes, oh, ow, fh, P);
+        const auto off = [&](const void *q) { return (size_t)(static_cast<const unsigned char *>(q) - smem); };
+        bool aligned = off(lds.raw) % 16 == 0 && fixed_pad(fh, ow) % 16 == 0 && sizeof(int2) * AGX_GLIMPSE_LIMIT <= (size_t)kMemTableBytes;
+        // the window image of glimpse i: (fh * ow) / 4 dwords at raw + i * fixed_pad (window_land, window_tail); the mask-out
+        // form reads the dword at (row, x), x + 4 <= ow
+        size_t end = off(lds.raw + (size_t)(P - 1) * fixed_pad(fh, ow)) + (size_t)((fh * ow) >> 2) * 4;
+        end = std::max(end, off(lds.raw + (size_t)P * fixed_pad(fh, ow)));
+        if (c.out_mode == AGX_OUT_RESIZE) {
+            aligned = aligned && off(lds.ytab_s) % 16 == 0 && sizeof(Tap) == 16;                       // ytab_stage: int4 stores
+            end = std::max(end, off(lds.ytab_s + oh));
+            float *h1 = lds.H + (size_t)fh * ow;                                                       // the second H of the double buffer
+            aligned = aligned && off(lds.H) % 16 == 0 && off(h1) % 16 == 0;                            // phase_d_quad: float4 reads
+            end = std::max(end, off(lds.H + 2 * (size_t)fh * ow));
+            if (!headline) {
+                float *acc = lds.H + 2 * (size_t)fh * ow;
+                aligned = aligned && off(acc) % 16 == 0;                                               // accL: float4
+                end = std::max(end, off(acc + (size_t)oh * ow));
+            }
+        }
+        const size_t lds_bytes = memory_lds(c, P, headline);
+        printf("P=%d end=%zu lds=%zu aligned=%d headline=%d\n", P, end, lds_bytes, (int)aligned, (int)headline);
+        if (end > lds_bytes || !aligned) bad = 1;
+    }
+    return bad;
+}
+
 int main(int argc, char **argv) {
+    if (argc > 1 && !strcmp(argv[1], "carve")) return carve_main(argc, argv);
     if (argc > 1 && !strcmp(argv[1], "k1plan")) return k1plan_main(argc, argv);
     if (argc > 1 && !strcmp(argv[1], "k1tables")) return k1tables_main(argc, argv);
     if (argc > 1 && !strcmp(argv[1], "plan")) return plan_main(argc, argv);
