@@ -471,6 +471,33 @@ class AtariVecEnv:
             out["weight"], out["priority"] = sampler.importance(beta), sampler.weight
         return out
 
+    def _rollout(self, who: str):
+        """The env's rollout.Rollout on its step log; ValueError without one."""
+        if self.steplog is None:
+            raise ValueError(f"{who} needs a step log (AtariEnvArgs.step_log = True, history_len > 0)")
+        from .rollout import Rollout
+        return Rollout(self.steplog)
+
+    def rollout_batch(self, L: int) -> dict:
+        """The last ``L`` transitions of every env, for an on-policy learner: ``rollout.Rollout(env.steplog).gather(L)`` with the
+        payload split into ``motor_action`` (i32 [L, N]) and, on a fixed env, ``sensory_action`` (f32 [L, N, 2]): the action taken
+        on seeing ``obs_index``.  Time-major; ``live`` marks the slots that hold a transition, ``ends`` where an episode ended
+        behind one and whether the return bootstraps there (rollout.TERMINATED / TRUNCATED / CUT / BOOT).  Read the observations
+        with ``env.history.observe(*Rollout.flat(batch))``.  Needs ``step_log``: ValueError otherwise."""
+        from .rollout import check_rollout_length
+        L = check_rollout_length(L)
+        out = self._rollout("rollout_batch").gather(L)
+        words = out.pop("payload").view(torch.int32)
+        out["motor_action"] = words[..., 0].contiguous()
+        if self.kind == "fixed":
+            out["sensory_action"] = words[..., 1:3].contiguous().view(torch.float32)
+        return out
+
+    def rollout_gae(self, batch: dict, value: torch.Tensor, boot_value: Optional[torch.Tensor], gamma: float = 0.99, lam: float = 0.95):
+        """GAE(lambda) over a ``rollout_batch`` -> (adv, ret), f32 [L, N]: ``rollout.Rollout(env.steplog).gae(...)``.  ``value`` is
+        the critic on ``obs_index``, ``boot_value`` the critic on ``next_index`` at the slots ``Rollout.boot_rows(batch)`` names."""
+        return self._rollout("rollout_gae").gae(batch, value, boot_value, gamma, lam)
+
     def update_priorities(self, batch: dict, td_error: torch.Tensor, alpha: float = 0.6, eps: float = 1e-6, **sampler_kw):
         """Write priority = (|td_error| + eps) ** alpha for the rows of a ``replay_batch(..., prioritized=True)`` batch; rows with
         ok = 0 are skipped, and so are rows evicted since the draw.  The table is that of the sampler the last prioritized

@@ -1287,3 +1287,4 @@ int agx_step_flexible_packed(agx_ctx *ctx, const uint8_t *d_screens, int screens
 #include "agx_priority_impl.h"
 #include "agx_augment_impl.h"
 #include "agx_sequence_impl.h"
+#include "agx_rollout_impl.h"
