@@ -74,6 +74,32 @@ def gae(length, reward, ends, value, boot, gamma, lam):
     return adv, ret
 
 
+def gae_vec(length, reward, ends, value, boot, gamma, lam):
+    """gae() with the envs as one np.float32 array per step: the same operations in the same order, one rounding each (NumPy
+    rounds every float32 array operation on its own), for the shapes a Python loop over L * N is too slow for.
+    tests/test_limit_cases_cpu.py holds it bit-equal to gae() on the cases above."""
+    L, N = reward.shape
+    gamma, lam = F32(gamma), F32(lam)
+    gl = F32(gamma * lam)
+    reward, value, ends = np.asarray(reward, F32), np.asarray(value, F32), np.asarray(ends)
+    first = L - np.clip(np.asarray(length, np.int64), 0, L)
+    adv, ret = np.zeros((L, N), F32), np.zeros((L, N), F32)
+    zero = np.zeros(N, F32)
+    A = zero
+    with np.errstate(all="ignore"):
+        for t in range(L - 1, -1, -1):
+            e, v = ends[t], value[t]
+            after = zero if t == L - 1 else np.where(e & TERMINATED, zero, value[t + 1])
+            nv = np.where(e & BOOT, zero if boot is None else np.asarray(boot[t], F32), after).astype(F32)
+            delta = ((reward[t] + gamma * nv).astype(F32) + (-v)).astype(F32)
+            carry = zero if t == L - 1 else np.where(e & 7, zero, (gl * A).astype(F32))
+            A = (delta + carry).astype(F32)
+            live = t >= first
+            adv[t], ret[t] = np.where(live, A, zero), np.where(live, (A + v).astype(F32), zero)
+            A = np.where(live, A, zero)                   # a slot that is not live is older than every live one: nothing reads this
+    return adv, ret
+
+
 # ---------------------------------------------------------------------------------------------- scripted scenarios
 # What one env does in one scripted step.  A step is up to two pushes and one record between them:
 #   STEP     push a frame, record it                                   TERM / TRUNC   ... with the end flag, then push the reset frame

@@ -159,6 +159,50 @@ def test_generic_geometry(kind, obs, fov, fs, mode, pad):
     pipe.close()
 
 
+# ---------------------------------------------------------------------------------------------- the pad at its limit
+PAD_LIMIT = 32                                             # AGX_SHIFT_PAD_LIMIT
+
+
+@gpu
+@pytest.mark.parametrize("obs, fov, fs, mode", [((84, 84), (30, 30), 4, m) for m in ("resize", "mask", "raw", "full")] +
+                         [((10, 12), (3, 5), 3, m) for m in ("resize", "mask", "raw", "full")],
+                         ids=lambda v: "x".join(map(str, v)) if isinstance(v, tuple) else str(v))
+def test_shifted_observe_at_pad_limit(obs, fov, fs, mode):
+    """pad = 32 (AGX_SHIFT_PAD_LIMIT; so far only the draw ran there), at the compile-time geometry 84 / 30 and at 10 x 12 / 3 x 5,
+    where every shift but the identity leaves the 3 x 5 crop, in every mode the geometry builds: the corners, the identity and
+    seeded random shifts over 0 .. 64 are bit for bit the gather of the unshifted output.  pad = 33 is refused by the library
+    (AGX_E_INVALID) and by the Python surface."""
+    from active_gym import FrameHistory, RandomShift
+    from active_gym import _native as nat
+    from active_gym import augment as ag
+    import ctypes
+    assert ag.PAD_LIMIT == PAD_LIMIT
+    what = "full" if mode == "full" else "fovea"
+    pipe = _pipe(4, obs=obs, fov=fov, fs=fs, mode="resize" if mode == "full" else mode, action_mode="relative")
+    hist = FrameHistory(pipe, 5)
+    model, rec = _run(pipe, hist, commands(11, 4, 9), 11)
+    samples = _samples(model)
+    issued, valid, _, evicted = _kinds(model, rec, samples)
+    assert valid >= 8 and evicted >= 1
+    aug = RandomShift(hist, pad=PAD_LIMIT)
+    for s in [(0, 0), (64, 64), (0, 64), (64, 0), (32, 32)]:
+        assert _check(pipe, hist, aug, samples, s, what) == valid
+    for seed in (3, 4):
+        shift = _random_shifts(len(samples), PAD_LIMIT, seed)
+        assert int(shift.max()) > 40 and int(shift.min()) < 24
+        assert _check(pipe, hist, aug, samples, shift, what) == valid
+    handle = ctypes.c_void_p()
+    assert ag.lib().agx_shift_create(hist.handle, PAD_LIMIT + 1, ctypes.byref(handle)) == nat.E_INVALID and not handle.value
+    assert ag.lib().agx_shift_create(hist.handle, -1, ctypes.byref(handle)) == nat.E_INVALID and not handle.value
+    what_code = 1 if what == "full" else 0                    # AGX_HIST_FULL / AGX_HIST_FOVEA: the pad is checked in front of the buffers
+    assert ag.lib().agx_history_observe_shifted(hist.handle, what_code, None, None, 4, None, 0, PAD_LIMIT + 1, None, None, None, None,
+                                                pipe._stream()) == nat.E_INVALID
+    assert "pad must be 0 .. 32, got 33" in nat.last_error(pipe._ctx)
+    with pytest.raises(ValueError, match="pad must be 0 .. 32"):
+        RandomShift(hist, pad=PAD_LIMIT + 1)
+    pipe.close()
+
+
 # ---------------------------------------------------------------------------------------------- 16-bit outputs
 @gpu
 @pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16], ids=["bf16", "f16"])
