@@ -179,6 +179,15 @@ class FrameHistory(Owner):
             aug = self._shifts[key] = RandomShift(self, pad, seed)
         return aug
 
+    def behaviour(self, width: int = 1):
+        """The one vtrace.BehaviourLog of this width on this history, made at first use."""
+        key = ("behaviour", int(width))
+        log = self._samplers.get(key)
+        if log is None:
+            from .vtrace import BehaviourLog
+            log = self._samplers[key] = BehaviourLog(self, width)
+        return log
+
     def transition_obs(self, read, env, index, next_index, shift=None) -> dict:
         """The observation part of a transition batch through ``read`` (``self.observe`` or a GlimpseMemory's): obs, next_obs
         and, on a fixed pipeline, fov_loc, next_fov_loc.  ``shift``: the augment.RandomShift whose ``observe`` ``read`` is - two

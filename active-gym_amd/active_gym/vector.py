@@ -498,6 +498,23 @@ class AtariVecEnv:
         the critic on ``obs_index``, ``boot_value`` the critic on ``next_index`` at the slots ``Rollout.boot_rows(batch)`` names."""
         return self._rollout("rollout_gae").gae(batch, value, boot_value, gamma, lam)
 
+    def rollout_vtrace(self, batch: dict, value: torch.Tensor, boot_value: Optional[torch.Tensor], rho: torch.Tensor, gamma: float = 0.99,
+                       lam: float = 1.0, rho_bar: float = 1.0, c_bar: float = 1.0, pg_rho_bar: float = 1.0):
+        """V-trace over a ``rollout_batch`` -> (vs, pg_adv), f32 [L, N]: ``vtrace.VTrace(env.steplog).returns(...)``, for a learner
+        whose actors lag it.  ``value`` and ``boot_value`` are ``rollout_gae``'s; ``rho`` is pi / mu of the action of every slot,
+        mu's log-probability being what ``env.behaviour_log()`` kept.  Needs ``step_log``: ValueError otherwise."""
+        if self.steplog is None:
+            raise ValueError("rollout_vtrace needs a step log (AtariEnvArgs.step_log = True, history_len > 0)")
+        from .vtrace import VTrace
+        return VTrace(self.steplog).returns(batch, value, boot_value, rho, gamma, lam, rho_bar, c_bar, pg_rho_bar)
+
+    def behaviour_log(self, width: int = 1):
+        """A vtrace.BehaviourLog on the env's frame history, cached per width: ``write(info["history_index"], logp)`` at every
+        act, ``read(batch["obs_index"])`` after ``rollout_batch``.  Needs ``history_len`` > 0: ValueError otherwise."""
+        if self.history is None:
+            raise ValueError("behaviour_log needs a frame history (AtariEnvArgs.history_len > 0)")
+        return self.history.behaviour(width)
+
     def update_priorities(self, batch: dict, td_error: torch.Tensor, alpha: float = 0.6, eps: float = 1e-6, **sampler_kw):
         """Write priority = (|td_error| + eps) ** alpha for the rows of a ``replay_batch(..., prioritized=True)`` batch; rows with
         ok = 0 are skipped, and so are rows evicted since the draw.  The table is that of the sampler the last prioritized

@@ -16,6 +16,7 @@
 //   k_history_observe_shifted / k_shift_draw  K10  random-shift augmentation: a retained observation moved by a drawn shift
 //   k_sequence_gather / k_sequence_observe  K11  sequence replay: L consecutive steps of one episode per sample, padded with zeros
 //   k_rollout_gather / k_rollout_gae  K12  on-policy rollouts: the last L transitions of every env, cut at episode ends, and GAE
+//   k_vtrace            K13 V-trace targets and policy-gradient advantages over a gathered rollout, for actor-learner training
 //
 // The fixed fovea's phases are stated once in agx_fixed_phases.h (K2, K5, K6, K10, K11 run them).  The three kernels that re-create
 // observation planes from history rows - k_history_observe, k_history_observe_shifted, k_sequence_observe - are one body,
@@ -41,6 +42,7 @@
 #include "agx_k10_augment.h"
 #include "agx_k11_sequence.h"
 #include "agx_k12_rollout.h"
+#include "agx_k13_vtrace.h"
 #include "agx_k34_resample.h"
 #include "agx_k3_per3.h"
 #include "agx_k4_flex3.h"
