@@ -79,6 +79,15 @@ class Rollout:
     def _check(self, rc):
         nat.check(rc, self.pipe._ctx)
 
+    def _fold_args(self, batch: dict, value: torch.Tensor, boot_value: Optional[torch.Tensor]):
+        """For gae and vtrace.VTrace.returns: (L, [the checked pointers of len, reward, ends, value, boot_value (None stays None)])."""
+        self._live()
+        L = check_rollout_length(batch["ends"].shape[0], self.num_envs)
+        n, chk = self.num_envs, self.pipe._chk
+        return L, [chk(batch["len"], (n,), torch.int32, "len"), chk(batch["reward"], (L, n), torch.float32, "reward"),
+                   chk(batch["ends"], (L, n), torch.uint8, "ends"), chk(value, (L, n), torch.float32, "value"),
+                   None if boot_value is None else chk(boot_value, (L, n), torch.float32, "boot_value")]
+
     def gather(self, L: int, out: Optional[dict] = None) -> dict:
         """The last L transitions of every env, as a dict: ``len`` i32 [N], and per slot ([L, N]) ``obs_index`` i64,
         ``next_index`` i64, ``reward`` f32, ``ends`` u8, ``payload`` u8 [L, N, W] (the action taken on seeing ``obs_index``) and
@@ -101,25 +110,16 @@ class Rollout:
             out["live"] = live
         return out
 
-    def _slots(self, t: torch.Tensor, name: str, L: int, optional: bool = False):
-        if t is None and optional:
-            return None
-        return self.pipe._chk(t, (L, self.num_envs), torch.float32, name)
-
     def gae(self, batch: dict, value: torch.Tensor, boot_value: Optional[torch.Tensor], gamma: float = 0.99, lam: float = 0.95,
             adv_out: Optional[torch.Tensor] = None, ret_out: Optional[torch.Tensor] = None):
         """GAE(lambda) over a gathered ``batch`` -> (adv, ret), f32 [L, N].  ``value``: f32 [L, N], the learner's value of
         ``obs_index``; ``boot_value``: f32 [L, N], its value of ``next_index``, used only at the slots ``boot_rows`` names (None
         only for a batch without such a slot).  A slot that is not live gets 0.  The fold is single precision with one rounding
         per operation, in the order of the header."""
-        self._live()
-        L = check_rollout_length(batch["ends"].shape[0], self.num_envs)
-        n, chk = self.num_envs, self.pipe._chk
-        pl, pr, pe = chk(batch["len"], (n,), torch.int32, "len"), self._slots(batch["reward"], "reward", L), chk(batch["ends"], (L, n), torch.uint8, "ends")
-        pv, pb = self._slots(value, "value", L), self._slots(boot_value, "boot_value", L, optional=True)
-        adv_out, pa = self.pipe._out(adv_out, (L, n), torch.float32, "adv_out")
-        ret_out, pt = self.pipe._out(ret_out, (L, n), torch.float32, "ret_out")
-        self._check(self._lib.agx_rollout_gae(self.history.handle, L, pl, pr, pe, pv, pb, float(gamma), float(lam), pa, pt, self.pipe._stream()))
+        L, args = self._fold_args(batch, value, boot_value)
+        adv_out, pa = self.pipe._out(adv_out, (L, self.num_envs), torch.float32, "adv_out")
+        ret_out, pt = self.pipe._out(ret_out, (L, self.num_envs), torch.float32, "ret_out")
+        self._check(self._lib.agx_rollout_gae(self.history.handle, L, *args, float(gamma), float(lam), pa, pt, self.pipe._stream()))
         return adv_out, ret_out
 
     def flat(self, batch: dict, which: str = "obs"):

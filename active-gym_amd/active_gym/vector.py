@@ -471,12 +471,13 @@ class AtariVecEnv:
             out["weight"], out["priority"] = sampler.importance(beta), sampler.weight
         return out
 
-    def _rollout(self, who: str):
-        """The env's rollout.Rollout on its step log; ValueError without one."""
+    def _rollout(self, who: str, vtrace: bool = False):
+        """The env's rollout.Rollout (vtrace: vtrace.VTrace) on its step log; ValueError without one."""
         if self.steplog is None:
             raise ValueError(f"{who} needs a step log (AtariEnvArgs.step_log = True, history_len > 0)")
         from .rollout import Rollout
-        return Rollout(self.steplog)
+        from .vtrace import VTrace
+        return (VTrace if vtrace else Rollout)(self.steplog)
 
     def rollout_batch(self, L: int) -> dict:
         """The last ``L`` transitions of every env, for an on-policy learner: ``rollout.Rollout(env.steplog).gather(L)`` with the
@@ -503,10 +504,7 @@ class AtariVecEnv:
         """V-trace over a ``rollout_batch`` -> (vs, pg_adv), f32 [L, N]: ``vtrace.VTrace(env.steplog).returns(...)``, for a learner
         whose actors lag it.  ``value`` and ``boot_value`` are ``rollout_gae``'s; ``rho`` is pi / mu of the action of every slot,
         mu's log-probability being what ``env.behaviour_log()`` kept.  Needs ``step_log``: ValueError otherwise."""
-        if self.steplog is None:
-            raise ValueError("rollout_vtrace needs a step log (AtariEnvArgs.step_log = True, history_len > 0)")
-        from .vtrace import VTrace
-        return VTrace(self.steplog).returns(batch, value, boot_value, rho, gamma, lam, rho_bar, c_bar, pg_rho_bar)
+        return self._rollout("rollout_vtrace", vtrace=True).returns(batch, value, boot_value, rho, gamma, lam, rho_bar, c_bar, pg_rho_bar)
 
     def behaviour_log(self, width: int = 1):
         """A vtrace.BehaviourLog on the env's frame history, cached per width: ``write(info["history_index"], logp)`` at every

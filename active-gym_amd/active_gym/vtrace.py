@@ -17,8 +17,8 @@ Every array is time-major ``[L, N]`` as ``Rollout.gather`` writes it; ``rho`` is
 logarithm, so the fold holds no transcendental and is bit-reproducible.  With ``rho == 1`` and levels >= 1, ``vs`` is
 ``Rollout.gae``'s ``ret`` bit for bit.  ``tests/vtrace_model.py`` restates the float32 fold in NumPy.
 
-The entry point lives in libagx.so, in a header and a binding of its own (active_gym/_native.py and active_gym/rollout.py are
-unchanged).  A VTrace owns no native handle; a BehaviourLog is one torch tensor and has no native code."""
+The entry point lives in libagx.so, in a header and a binding of its own (active_gym/_native.py is unchanged).  A VTrace is
+a Rollout with ``returns`` next to ``gae``; it owns no native handle; a BehaviourLog is one torch tensor and has no native code."""
 from __future__ import annotations
 
 import ctypes as C
@@ -28,7 +28,7 @@ from typing import Optional
 import torch
 
 from . import _native as nat
-from .rollout import check_rollout_length
+from .rollout import Rollout
 
 _P = C.c_void_p
 
@@ -52,18 +52,12 @@ def check_bars(rho_bar, c_bar, pg_rho_bar):
     return tuple(out)
 
 
-class VTrace:
+class VTrace(Rollout):
     def __init__(self, steplog):
-        """steplog: the StepLog whose gathered rollouts are folded; its history supplies N and the device."""
-        self._lib = lib()
-        self.steplog = steplog
-        self.history = steplog.history
-        self.pipe = steplog.pipe
-        self.device = steplog.device
-        self.num_envs = steplog.num_envs
-
-    def _live(self):
-        self.steplog._live()          # (the history closes its logs first: an open log has an open history)
+        """steplog: the StepLog whose gathered rollouts are folded; its history supplies N and the device.  The constructor, the
+        liveness check and the marshalling of a batch are Rollout's."""
+        super().__init__(steplog)
+        self._lib = lib()             # (the same library, with this module's SIGNATURES bound too)
 
     def returns(self, batch: dict, value: torch.Tensor, boot_value: Optional[torch.Tensor], rho: torch.Tensor, gamma: float = 0.99,
                 lam: float = 1.0, rho_bar: float = 1.0, c_bar: float = 1.0, pg_rho_bar: float = 1.0,
@@ -75,16 +69,13 @@ class VTrace:
         the policy gradient; each must be > 0 and ``inf`` means no clipping.  A slot that is not live gets 0.  The fold is single
         precision with one rounding per operation, in the order of the header."""
         rho_bar, c_bar, pg_rho_bar = check_bars(rho_bar, c_bar, pg_rho_bar)
-        self._live()
-        L = check_rollout_length(batch["ends"].shape[0], self.num_envs)
-        n, chk = self.num_envs, self.pipe._chk
-        pl, pe = chk(batch["len"], (n,), torch.int32, "len"), chk(batch["ends"], (L, n), torch.uint8, "ends")
-        pr, pv, pw = (chk(t, (L, n), torch.float32, name) for t, name in ((batch["reward"], "reward"), (value, "value"), (rho, "rho")))
-        pb = None if boot_value is None else chk(boot_value, (L, n), torch.float32, "boot_value")
+        L, args = self._fold_args(batch, value, boot_value)
+        n = self.num_envs
+        pw = self.pipe._chk(rho, (L, n), torch.float32, "rho")
         vs_out, ps = self.pipe._out(vs_out, (L, n), torch.float32, "vs_out")
         pg_adv_out, pg = self.pipe._out(pg_adv_out, (L, n), torch.float32, "pg_adv_out")
-        nat.check(self._lib.agx_vtrace_returns(self.history.handle, L, pl, pr, pe, pv, pb, pw, float(gamma), float(lam), rho_bar, c_bar,
-                                               pg_rho_bar, ps, pg, self.pipe._stream()), self.pipe._ctx)
+        self._check(self._lib.agx_vtrace_returns(self.history.handle, L, *args, pw, float(gamma), float(lam), rho_bar, c_bar, pg_rho_bar, ps, pg,
+                                                 self.pipe._stream()))
         return vs_out, pg_adv_out
 
 

@@ -1,10 +1,11 @@
 // agx_k12_rollout.h - K12: on-policy rollouts on the step log (include/agx_rollout.h).  k_rollout_gather walks every env's rows
-// backward from its newest and writes the last L transitions, k_rollout_gae folds GAE(lambda) over them.  The rule and the fold
-// are agx_rollout_math.h's, the validity of an observation agx_hist_rule.h's: nothing is restated here.  Every device write is
+// backward from its newest and writes the last L transitions, k_slot_fold<GaeFold> folds GAE(lambda) over them.  The rule and the
+// fold are agx_rollout_math.h's, the validity of an observation agx_hist_rule.h's: nothing is restated here.  Every device write is
 // an ordinary vector store.
 #pragma once
 #include "agx_k8_steplog.h"
 #include "agx_rollout_math.h"
+#include "agx_slot_fold.h"
 
 namespace agx {
 
@@ -70,17 +71,11 @@ __global__ __launch_bounds__(kThreads) void k_rollout_gather(StepLogParams p, in
 }
 
 // ---------------------------------------------------------------------------------------------
-// k_rollout_gae<BOOT>: block = 64 = one wave, one env per thread, grid = ceil(N / 64): N = 1024 spreads over 16 CUs.  The arrays
-// are time-major, so every load and store of a step is coalesced across the envs of a wave.  The fold is a serial chain per env,
-// so the loads must not sit on it: the kernel keeps two register sets of kGaeAhead steps, issues the loads of the next set
-// - they depend on nothing but t - and then folds the current one (gae_step, in the order of the header: nothing is
-// reassociated).  A slot is addressed by its 32-bit element number (L * N <= INT32_MAX), which goes down by N per step: the
-// step offsets are wave-uniform and stay on the scalar unit.  Only the last set can be short (the L mod kGaeAhead oldest
-// slots): its loads are clamped to its oldest slot and its fold stops there (FULL = false).  A slot that is not live is folded
-// too and then written as 0: the live slots are the newest ones, so nothing the fold made of a padded slot reaches them.
-// BOOT = false: d_boot_value is NULL and reads as 0.
+// GAE(lambda) over the gathered slots: k_slot_fold<GaeFold, BOOT> (agx_slot_fold.h), folding every step with gae_step.
 // ---------------------------------------------------------------------------------------------
-constexpr int kGaeThreads = 64, kGaeAhead = 16;
+#ifndef AGX_GAE_AHEAD
+#define AGX_GAE_AHEAD 16             // the set depth; 8 has not been measured in this form (DESIGN.md sections 21 and 23)
+#endif
 
 struct GaeParams {
     const int32_t *len;          // [N]
@@ -92,71 +87,29 @@ struct GaeParams {
     float gamma, lambda;
 };
 
-struct GaeSet {
-    float r[kGaeAhead], v[kGaeAhead], b[kGaeAhead];
-    uint32_t e[kGaeAhead];
-};
-
-// the cnt slots from element `at` (slot t0 of the thread's env) downward; FULL: cnt == kGaeAhead
-template <bool BOOT, bool FULL>
-__device__ __forceinline__ void gae_load(GaeSet &s, const GaeParams &q, uint32_t at, int cnt) {
-#pragma unroll
-    for (int i = 0; i < kGaeAhead; ++i) {
-        const uint32_t a = at - (uint32_t)(FULL ? i : min(i, cnt - 1)) * (uint32_t)q.N;
+struct GaeFold {
+    using Params = GaeParams;
+    using Out = GaeOut;
+    static constexpr int kAhead = AGX_GAE_AHEAD;
+    struct Set {
+        float r[kAhead], v[kAhead], b[kAhead];
+        uint32_t e[kAhead];
+    };
+    static __device__ __forceinline__ float coef(const Params &q) { return steplog_fmul(q.gamma, q.lambda); }
+    template <bool BOOT>
+    static __device__ __forceinline__ void load(Set &s, int i, const Params &q, uint32_t a) {
         s.r[i] = q.reward[a];
         s.v[i] = q.value[a];
         s.e[i] = q.ends[a];
         s.b[i] = BOOT ? q.boot[a] : 0.0f;
     }
-}
-
-template <bool FULL>
-__device__ __forceinline__ void gae_fold_set(const GaeSet &s, const GaeParams &q, uint32_t at, int t0, int cnt, int first, float gl, float &A,
-                                             float &vnext) {
-#pragma unroll
-    for (int i = 0; i < kGaeAhead; ++i) {
-        if (FULL || i < cnt) {                                       // (uniform: cnt depends on nothing of the env)
-            const int t = t0 - i;
-            const GaeOut g = gae_step(A, s.e[i], t == q.L - 1, s.r[i], s.v[i], vnext, s.b[i], q.gamma, gl);
-            vnext = s.v[i];
-            const uint32_t a = at - (uint32_t)i * (uint32_t)q.N;
-            q.adv[a] = t >= first ? g.adv : 0.0f;
-            q.ret[a] = t >= first ? g.ret : 0.0f;
-        }
+    static __device__ __forceinline__ Out step(float &A, const Set &s, int i, bool newest, float vnext, const Params &q, float gl) {
+        return gae_step(A, s.e[i], newest, s.r[i], s.v[i], vnext, s.b[i], q.gamma, gl);
     }
-}
-
-template <bool BOOT>
-__global__ __launch_bounds__(kGaeThreads) void k_rollout_gae(GaeParams q) {
-    const int n = blockIdx.x * kGaeThreads + threadIdx.x;
-    if (n >= q.N) return;
-    const int first = q.L - min(max(q.len[n], 0), q.L);
-    const float gl = steplog_fmul(q.gamma, q.lambda);
-    const uint32_t stride = (uint32_t)kGaeAhead * (uint32_t)q.N;
-    float A = 0.0f, vnext = 0.0f;
-    int t0 = q.L - 1, cnt = min(kGaeAhead, q.L);
-    uint32_t at = (uint32_t)t0 * (uint32_t)q.N + (uint32_t)n;
-    GaeSet cur, nxt;
-    if (cnt == kGaeAhead)
-        gae_load<BOOT, true>(cur, q, at, cnt);
-    else
-        gae_load<BOOT, false>(cur, q, at, cnt);
-    for (;;) {
-        const int ahead = min(kGaeAhead, t0 + 1 - cnt);              // the slots of the next set; a short set is the last one
-        if (ahead == kGaeAhead)
-            gae_load<BOOT, true>(nxt, q, at - stride, ahead);
-        else if (ahead > 0)
-            gae_load<BOOT, false>(nxt, q, at - stride, ahead);
-        if (cnt == kGaeAhead)
-            gae_fold_set<true>(cur, q, at, t0, cnt, first, gl, A, vnext);
-        else
-            gae_fold_set<false>(cur, q, at, t0, cnt, first, gl, A, vnext);
-        if (ahead == 0) break;
-        cur = nxt;
-        t0 -= kGaeAhead;
-        at -= stride;
-        cnt = ahead;
+    static __device__ __forceinline__ void store(const Params &q, uint32_t a, bool live, const Out &g) {
+        q.adv[a] = live ? g.adv : 0.0f;
+        q.ret[a] = live ? g.ret : 0.0f;
     }
-}
+};
 
 }  // namespace agx

@@ -15,13 +15,14 @@
 //   k_priority_weights / _chunks / _scan / _draw / _update / _lookup  K9  prioritized sampler: draw proportionally to a priority
 //   k_history_observe_shifted / k_shift_draw  K10  random-shift augmentation: a retained observation moved by a drawn shift
 //   k_sequence_gather / k_sequence_observe  K11  sequence replay: L consecutive steps of one episode per sample, padded with zeros
-//   k_rollout_gather / k_rollout_gae  K12  on-policy rollouts: the last L transitions of every env, cut at episode ends, and GAE
-//   k_vtrace            K13 V-trace targets and policy-gradient advantages over a gathered rollout, for actor-learner training
+//   k_rollout_gather / k_slot_fold<GaeFold>  K12  on-policy rollouts: the last L transitions of every env, cut at episode ends, and GAE
+//   k_slot_fold<VtraceFold>  K13 V-trace targets and policy-gradient advantages over a gathered rollout, for actor-learner training
 //
 // The fixed fovea's phases are stated once in agx_fixed_phases.h (K2, K5, K6, K10, K11 run them).  The three kernels that re-create
 // observation planes from history rows - k_history_observe, k_history_observe_shifted, k_sequence_observe - are one body,
 // agx_hist_plane.h (sample resolution, source row, position, plane write), under their own indexing and shift policy; the
-// validity rule of a history sample is agx_hist_rule.h's.
+// validity rule of a history sample is agx_hist_rule.h's.  The backward folds over a gathered rollout - GAE and V-trace - are one kernel,
+// agx_slot_fold.h's k_slot_fold, under a policy each (streams, step, outputs, set depth).
 //
 // Persistent per-env state (owned by the context, see agx_api.hip):
 //   ring  u8 [N][fs][oh][ow]   numerators k of the reference's float32 k/255 frames

@@ -8,10 +8,22 @@ static_assert(AGX_ROLLOUT_LIMIT == agx::kRolloutLimit && AGX_ROLLOUT_CUT == agx:
 
 namespace {
 
-// the argument checks the two entry points share behind the handle, in the header's order: L, then L * N
+// the argument checks every entry point here and in agx_vtrace_impl.h shares behind the handle, in the headers' order: L, then L * N
 int rollout_bad_L(agx_ctx *ctx, const char *who, int32_t L, int32_t N) {
     if (L < 1 || L > AGX_ROLLOUT_LIMIT) return fail(ctx, AGX_E_INVALID, "%s: L must be 1 .. %d, got %d", who, AGX_ROLLOUT_LIMIT, L);
     if ((int64_t)L * N > INT32_MAX) return fail(ctx, AGX_E_INVALID, "%s: L * N = %lld exceeds %d", who, (long long)L * N, INT32_MAX);
+    return AGX_OK;
+}
+
+// the launch of k_slot_fold<F, BOOT> over the N envs of q: one env per thread
+template <class F>
+int launch_slot_fold(agx_ctx *ctx, const typename F::Params &q, bool boot, void *stream) {
+    const uint32_t blocks = (uint32_t)((q.N + agx::kFoldThreads - 1) / agx::kFoldThreads);
+    if (boot)
+        hipLaunchKernelGGL((agx::k_slot_fold<F, true>), dim3(blocks), dim3(agx::kFoldThreads), 0, S(stream), q);
+    else
+        hipLaunchKernelGGL((agx::k_slot_fold<F, false>), dim3(blocks), dim3(agx::kFoldThreads), 0, S(stream), q);
+    AGX_HIP(ctx, hipGetLastError());
     return AGX_OK;
 }
 
@@ -55,13 +67,7 @@ int agx_rollout_gae(agx_history *h, int32_t L, const int32_t *d_len, const float
     if (!full_range(ctx)) return hist_refuse_range(h, who);
     DeviceGuard g(ctx->cfg.device);
     const agx::GaeParams q{d_len, d_reward, d_ends, d_value, d_boot_value, d_adv, d_ret, N, L, gamma, lambda};
-    const uint32_t blocks = (uint32_t)((N + agx::kGaeThreads - 1) / agx::kGaeThreads);
-    if (d_boot_value)
-        hipLaunchKernelGGL(agx::k_rollout_gae<true>, dim3(blocks), dim3(agx::kGaeThreads), 0, S(stream), q);
-    else
-        hipLaunchKernelGGL(agx::k_rollout_gae<false>, dim3(blocks), dim3(agx::kGaeThreads), 0, S(stream), q);
-    AGX_HIP(ctx, hipGetLastError());
-    return AGX_OK;
+    return launch_slot_fold<agx::GaeFold>(ctx, q, d_boot_value != nullptr, stream);
 }
 
 }  // extern "C"

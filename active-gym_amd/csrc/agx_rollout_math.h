@@ -1,15 +1,13 @@
 // agx_rollout_math.h - the rule of an on-policy rollout on the step log and the GAE fold (include/agx_rollout.h), as
-// __host__ __device__ functions over an accessor argument: k_rollout_gather / k_rollout_gae (agx_k12_rollout.h) decide every row
+// __host__ __device__ functions over an accessor argument: k_rollout_gather / k_slot_fold<GaeFold> (agx_k12_rollout.h) decide every row
 // with rollout_row and rollout_ends and fold every step with gae_step, and a plain C++ program (tests/rollout_harness.cpp) runs
-// rollout_walk and gae_fold, the loops over the very same three.  Nothing here touches the GPU.
+// rollout_walk and gae_fold, the loops over the very same three (gae_fold is agx_fold_math.h's slot_fold).  Nothing here touches the GPU.
 #pragma once
-#include "agx_steplog_fold.h"
+#include "agx_fold_math.h"
 
 namespace agx {
 
 constexpr int32_t kRolloutLimit = 4096;                          // AGX_ROLLOUT_LIMIT
-constexpr uint32_t kRolloutCut = 4, kRolloutBoot = 8;            // AGX_ROLLOUT_CUT, AGX_ROLLOUT_BOOT
-constexpr uint32_t kRolloutBreak = kStepTerminated | kStepTruncated | kRolloutCut;      // the bits that end an episode's chain
 
 enum RolloutRow : int { kRolloutTake = 0, kRolloutSkip = 1, kRolloutStop = 2 };
 
@@ -54,28 +52,25 @@ struct GaeOut {
     float adv, ret;
 };
 AGX_HD GaeOut gae_step(float &A, uint32_t e, bool newest, float reward, float value, float value_next, float boot, float gamma, float gl) {
-    const float nv = (e & kRolloutBoot) ? boot : ((e & kStepTerminated) || newest) ? 0.0f : value_next;
+    const float nv = fold_next_value(e, newest, value_next, boot);
     const float delta = steplog_fadd(steplog_fadd(reward, steplog_fmul(gamma, nv)), -value);
-    const float carry = (newest || (e & kRolloutBreak)) ? 0.0f : steplog_fmul(gl, A);
+    const float carry = fold_breaks(e, newest) ? 0.0f : steplog_fmul(gl, A);
     A = steplog_fadd(delta, carry);
     return GaeOut{A, steplog_fadd(A, value)};
 }
 
-// The whole fold of one env.  at(t) places slot t of the env in the [L][N] arrays; boot may be nullptr (reads as 0).
+// The whole fold of one env: slot_fold over gae_step.  at(t) places slot t of the env in the [L][N] arrays; boot may be nullptr
+// (reads as 0).
 template <class At>
 AGX_HD void gae_fold(const At &at, int32_t L, int32_t len, const float *reward, const uint8_t *ends, const float *value, const float *boot,
                      float gamma, float lambda, float *adv, float *ret) {
     const float gl = steplog_fmul(gamma, lambda);
-    const int32_t first = L - (len < 0 ? 0 : len > L ? L : len);
-    float A = 0.0f;
-    for (int32_t t = L - 1; t >= 0; --t) {
-        const auto i = at(t);
-        GaeOut o{0.0f, 0.0f};
-        if (t >= first)
-            o = gae_step(A, ends[i], t == L - 1, reward[i], value[i], t == L - 1 ? 0.0f : value[at(t + 1)], boot ? boot[i] : 0.0f, gamma, gl);
-        adv[i] = o.adv;
-        ret[i] = o.ret;
-    }
+    slot_fold<GaeOut>(
+        at, L, len,
+        [&](float &A, auto i, bool newest, auto i_next) {
+            return gae_step(A, ends[i], newest, reward[i], value[i], newest ? 0.0f : value[i_next], boot ? boot[i] : 0.0f, gamma, gl);
+        },
+        [&](auto i, const GaeOut &o) { adv[i] = o.adv, ret[i] = o.ret; });
 }
 
 }  // namespace agx

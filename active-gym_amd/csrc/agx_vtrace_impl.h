@@ -1,11 +1,10 @@
 // agx_vtrace_impl.h - the V-trace fold declared in include/agx_vtrace.h (included at the end of agx_api.hip, behind the frame
-// history and the rollouts whose arrays it reads): the checks and the launch of agx_k13_vtrace.h.  It owns no handle and no memory.
+// history and agx_rollout_impl.h, whose arrays it reads and whose L check and fold launch it shares): the checks of K13
+// (agx_k13_vtrace.h).  It owns no handle and no memory.
 #pragma once
 #include "agx_vtrace.h"
 
 static_assert(AGX_VTRACE_LIMIT == agx::kVtraceLimit && AGX_VTRACE_LIMIT == AGX_ROLLOUT_LIMIT, "the limit is that of a gathered rollout");
-static_assert(agx::kVtraceBoot == AGX_ROLLOUT_BOOT && agx::kVtraceBreak == (AGX_STEP_TERMINATED | AGX_STEP_TRUNCATED | AGX_ROLLOUT_CUT),
-              "agx_vtrace_math.h reads the ends byte the rollout gather writes");
 
 extern "C" {
 
@@ -16,8 +15,7 @@ int agx_vtrace_returns(agx_history *h, int32_t L, const int32_t *d_len, const fl
     if (!h) return fail(nullptr, AGX_E_INVALID, "%s: null argument (h)", who);
     agx_ctx *ctx = h->ctx;
     const int32_t N = h->p.N;
-    if (L < 1 || L > AGX_VTRACE_LIMIT) return fail(ctx, AGX_E_INVALID, "%s: L must be 1 .. %d, got %d", who, AGX_VTRACE_LIMIT, L);
-    if ((int64_t)L * N > INT32_MAX) return fail(ctx, AGX_E_INVALID, "%s: L * N = %lld exceeds %d", who, (long long)L * N, INT32_MAX);
+    if (int rc = rollout_bad_L(ctx, who, L, N)) return rc;
     if (!d_len || !d_reward || !d_ends || !d_value || !d_rho || !d_vs || !d_pg_adv)
         return fail(ctx, AGX_E_INVALID, "%s: null buffer (%s)", who,
                     !d_len ? "d_len" : !d_reward ? "d_reward" : !d_ends ? "d_ends" : !d_value ? "d_value" : !d_rho ? "d_rho" : !d_vs ? "d_vs" : "d_pg_adv");
@@ -27,13 +25,7 @@ int agx_vtrace_returns(agx_history *h, int32_t L, const int32_t *d_len, const fl
     if (!full_range(ctx)) return hist_refuse_range(h, who);
     DeviceGuard g(ctx->cfg.device);
     const agx::VtraceParams q{d_len, d_reward, d_ends, d_value, d_boot_value, d_rho, d_vs, d_pg_adv, N, L, {gamma, lambda, rho_bar, c_bar, pg_rho_bar}};
-    const uint32_t blocks = (uint32_t)((N + agx::kVtraceThreads - 1) / agx::kVtraceThreads);
-    if (d_boot_value)
-        hipLaunchKernelGGL(agx::k_vtrace<true>, dim3(blocks), dim3(agx::kVtraceThreads), 0, S(stream), q);
-    else
-        hipLaunchKernelGGL(agx::k_vtrace<false>, dim3(blocks), dim3(agx::kVtraceThreads), 0, S(stream), q);
-    AGX_HIP(ctx, hipGetLastError());
-    return AGX_OK;
+    return launch_slot_fold<agx::VtraceFold>(ctx, q, d_boot_value != nullptr, stream);
 }
 
 }  // extern "C"

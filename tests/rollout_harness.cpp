@@ -1,5 +1,5 @@
-// The __host__ side of active-gym_amd/csrc/agx_rollout_math.h - the very functions k_rollout_gather and k_rollout_gae decide every
-// row and fold every step with - on host arrays.
+// The __host__ side of active-gym_amd/csrc/agx_rollout_math.h - the very functions k_rollout_gather and k_slot_fold<GaeFold> decide
+// every row and fold every step with - on host arrays.
 //
 //     rollout_harness <file>            the tokens below, whitespace separated, read from a file
 //     rollout_harness <token> ...       ... or given as arguments
@@ -11,25 +11,12 @@
 // Floats travel as the decimal value of their 32-bit pattern.
 #include <cinttypes>
 #include <cstdio>
-#include <cstdlib>
-#include <cstring>
 #include <string>
-#include <vector>
 
 #include "agx_rollout_math.h"
+#include "harness_tokens.h"
 
 namespace {
-
-float from_bits(uint32_t u) {
-    float f;
-    memcpy(&f, &u, sizeof f);
-    return f;
-}
-uint32_t to_bits(float f) {
-    uint32_t u;
-    memcpy(&u, &f, sizeof u);
-    return u;
-}
 
 struct HostRows {
     int32_t T, N, n;
@@ -43,42 +30,22 @@ struct HostRows {
 }  // namespace
 
 int main(int argc, char **argv) {
-    std::vector<std::string> tok;
-    if (argc == 2) {
-        FILE *f = fopen(argv[1], "r");
-        if (!f) {
-            fprintf(stderr, "cannot open %s\n", argv[1]);
-            return 2;
-        }
-        char buf[64];
-        while (fscanf(f, "%63s", buf) == 1) tok.emplace_back(buf);
-        fclose(f);
-    } else {
-        for (int i = 1; i < argc; ++i) tok.emplace_back(argv[i]);
-    }
-    size_t at = 0;
-    bool short_input = false;
-    auto next = [&]() -> int64_t {
-        if (at >= tok.size()) {
-            short_input = true;
-            return 0;
-        }
-        return strtoll(tok[at++].c_str(), nullptr, 10);
-    };
-    const int64_t what = next();
+    Tokens in;
+    if (!in.read(argc, argv)) return 2;
+    const int64_t what = in.next();
     if (what == 0) {
-        const int32_t T = (int32_t)next(), N = (int32_t)next(), fs = (int32_t)next(), L = (int32_t)next();
-        if (short_input || T <= 0 || N <= 0 || fs < 1 || L < 1 || L > agx::kRolloutLimit) {
+        const int32_t T = (int32_t)in.next(), N = (int32_t)in.next(), fs = (int32_t)in.next(), L = (int32_t)in.next();
+        if (in.short_input || T <= 0 || N <= 0 || fs < 1 || L < 1 || L > agx::kRolloutLimit) {
             fprintf(stderr, "usage: %s <file> | 0 T N fs L count[N] age[T*N] stamp[T*N] flags[T*N]\n", argv[0]);
             return 2;
         }
         const size_t rows = (size_t)T * N;
         std::vector<int64_t> count(N), age(rows), stamp(rows), flags(rows);
-        for (auto &v : count) v = next();
-        for (auto &v : age) v = next();
-        for (auto &v : stamp) v = next();
-        for (auto &v : flags) v = next();
-        if (short_input || at != tok.size()) {
+        for (auto &v : count) v = in.next();
+        for (auto &v : age) v = in.next();
+        for (auto &v : stamp) v = in.next();
+        for (auto &v : flags) v = in.next();
+        if (!in.complete()) {
             fprintf(stderr, "%s: the arrays are incomplete or over-long\n", argv[0]);
             return 2;
         }
@@ -95,10 +62,10 @@ int main(int argc, char **argv) {
         return 0;
     }
     if (what == 1) {
-        const int32_t N = (int32_t)next(), L = (int32_t)next();
-        const float gamma = from_bits((uint32_t)next()), lambda = from_bits((uint32_t)next());
-        const bool has_boot = next() != 0;
-        if (short_input || N <= 0 || L < 1 || L > agx::kRolloutLimit) {
+        const int32_t N = (int32_t)in.next(), L = (int32_t)in.next();
+        const float gamma = in.next_float(), lambda = in.next_float();
+        const bool has_boot = in.next() != 0;
+        if (in.short_input || N <= 0 || L < 1 || L > agx::kRolloutLimit) {
             fprintf(stderr, "usage: %s <file> | 1 N L gamma_bits lambda_bits has_boot len[N] reward_bits[L*N] ends[L*N] value_bits[L*N] [boot_bits[L*N]]\n",
                     argv[0]);
             return 2;
@@ -107,12 +74,12 @@ int main(int argc, char **argv) {
         std::vector<int32_t> len(N);
         std::vector<float> reward(slots), value(slots), boot(has_boot ? slots : 0), adv(slots), ret(slots);
         std::vector<uint8_t> ends(slots);
-        for (auto &v : len) v = (int32_t)next();
-        for (auto &v : reward) v = from_bits((uint32_t)next());
-        for (auto &v : ends) v = (uint8_t)next();
-        for (auto &v : value) v = from_bits((uint32_t)next());
-        for (auto &v : boot) v = from_bits((uint32_t)next());
-        if (short_input || at != tok.size()) {
+        for (auto &v : len) v = (int32_t)in.next();
+        for (auto &v : reward) v = in.next_float();
+        for (auto &v : ends) v = (uint8_t)in.next();
+        for (auto &v : value) v = in.next_float();
+        for (auto &v : boot) v = in.next_float();
+        if (!in.complete()) {
             fprintf(stderr, "%s: the arrays are incomplete or over-long\n", argv[0]);
             return 2;
         }

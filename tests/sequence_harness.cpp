@@ -7,11 +7,9 @@
 // tokens: T N fs L, count[N], age[T*N] (rows [t][n]), then any number of samples "n k".  Per sample one line: its length.
 #include <cinttypes>
 #include <cstdio>
-#include <cstdlib>
-#include <string>
-#include <vector>
 
 #include "agx_sequence_math.h"
+#include "harness_tokens.h"
 
 namespace {
 
@@ -25,43 +23,23 @@ struct HostRows {
 }  // namespace
 
 int main(int argc, char **argv) {
-    std::vector<std::string> tok;
-    if (argc == 2) {
-        FILE *f = fopen(argv[1], "r");
-        if (!f) {
-            fprintf(stderr, "cannot open %s\n", argv[1]);
-            return 2;
-        }
-        char buf[64];
-        while (fscanf(f, "%63s", buf) == 1) tok.emplace_back(buf);
-        fclose(f);
-    } else {
-        for (int i = 1; i < argc; ++i) tok.emplace_back(argv[i]);
-    }
-    size_t at = 0;
-    bool short_input = false;
-    auto next = [&]() -> int64_t {
-        if (at >= tok.size()) {
-            short_input = true;
-            return 0;
-        }
-        return strtoll(tok[at++].c_str(), nullptr, 10);
-    };
-    const int32_t T = (int32_t)next(), N = (int32_t)next(), fs = (int32_t)next(), L = (int32_t)next();
-    if (short_input || T <= 0 || N <= 0 || fs < 1 || L < 1 || L > agx::kSequenceLimit) {
+    Tokens in;
+    if (!in.read(argc, argv)) return 2;
+    const int32_t T = (int32_t)in.next(), N = (int32_t)in.next(), fs = (int32_t)in.next(), L = (int32_t)in.next();
+    if (in.short_input || T <= 0 || N <= 0 || fs < 1 || L < 1 || L > agx::kSequenceLimit) {
         fprintf(stderr, "usage: %s <file> | T N fs L count[N] age[T*N] [n k ...]\n", argv[0]);
         return 2;
     }
     const size_t rows = (size_t)T * N;
     std::vector<int64_t> count(N), age(rows);
-    for (auto &v : count) v = next();
-    for (auto &v : age) v = next();
-    if (short_input || (tok.size() - at) % 2) {
+    for (auto &v : count) v = in.next();
+    for (auto &v : age) v = in.next();
+    if (in.short_input || in.left() % 2) {
         fprintf(stderr, "%s: the arrays are incomplete or a sample lacks its index\n", argv[0]);
         return 2;
     }
-    while (at < tok.size()) {
-        const int64_t n = next(), k = next();
+    while (in.left()) {
+        const int64_t n = in.next(), k = in.next();
         const bool env = n >= 0 && n < N;
         const HostRows r{T, N, env ? (int32_t)n : 0, age.data()};
         printf("%d\n", agx::sequence_length(r, env, k, env ? count[n] : 0, T, fs, L));

@@ -8,25 +8,11 @@
 // "steps next_index flags return_bits discount_bits" ("0 -1 - - -" for a sample that folded no row).
 #include <cinttypes>
 #include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <string>
-#include <vector>
 
 #include "agx_steplog_fold.h"
+#include "harness_tokens.h"
 
 namespace {
-
-float from_bits(uint32_t u) {
-    float f;
-    memcpy(&f, &u, sizeof f);
-    return f;
-}
-uint32_t to_bits(float f) {
-    uint32_t u;
-    memcpy(&u, &f, sizeof u);
-    return u;
-}
 
 struct HostRows {
     int32_t T, N, n;
@@ -43,48 +29,28 @@ struct HostRows {
 }  // namespace
 
 int main(int argc, char **argv) {
-    std::vector<std::string> tok;
-    if (argc == 2) {
-        FILE *f = fopen(argv[1], "r");
-        if (!f) {
-            fprintf(stderr, "cannot open %s\n", argv[1]);
-            return 2;
-        }
-        char buf[64];
-        while (fscanf(f, "%63s", buf) == 1) tok.emplace_back(buf);
-        fclose(f);
-    } else {
-        for (int i = 1; i < argc; ++i) tok.emplace_back(argv[i]);
-    }
-    size_t at = 0;
-    bool short_input = false;
-    auto next = [&]() -> int64_t {
-        if (at >= tok.size()) {
-            short_input = true;
-            return 0;
-        }
-        return strtoll(tok[at++].c_str(), nullptr, 10);
-    };
-    const int32_t T = (int32_t)next(), N = (int32_t)next(), nstep = (int32_t)next();
-    const float gamma = from_bits((uint32_t)next());
-    if (short_input || T <= 0 || N <= 0 || nstep < 1) {
+    Tokens in;
+    if (!in.read(argc, argv)) return 2;
+    const int32_t T = (int32_t)in.next(), N = (int32_t)in.next(), nstep = (int32_t)in.next();
+    const float gamma = in.next_float();
+    if (in.short_input || T <= 0 || N <= 0 || nstep < 1) {
         fprintf(stderr, "usage: %s <file> | T N nstep gamma_bits count[N] age[T*N] stamp[T*N] reward_bits[T*N] flags[T*N] [n k ...]\n", argv[0]);
         return 2;
     }
     const size_t rows = (size_t)T * N;
     std::vector<int64_t> count(N), age(rows), stamp(rows), flags(rows);
     std::vector<float> reward(rows);
-    for (auto &v : count) v = next();
-    for (auto &v : age) v = next();
-    for (auto &v : stamp) v = next();
-    for (auto &v : reward) v = from_bits((uint32_t)next());
-    for (auto &v : flags) v = next();
-    if (short_input || (tok.size() - at) % 2) {
+    for (auto &v : count) v = in.next();
+    for (auto &v : age) v = in.next();
+    for (auto &v : stamp) v = in.next();
+    for (auto &v : reward) v = in.next_float();
+    for (auto &v : flags) v = in.next();
+    if (in.short_input || in.left() % 2) {
         fprintf(stderr, "%s: the arrays are incomplete or a sample lacks its index\n", argv[0]);
         return 2;
     }
-    while (at < tok.size()) {
-        const int64_t n = next(), k = next();
+    while (in.left()) {
+        const int64_t n = in.next(), k = in.next();
         const bool env = n >= 0 && n < N;
         const int64_t cnt = env ? count[n] : 0;
         const HostRows r{T, N, env ? (int32_t)n : 0, age.data(), stamp.data(), reward.data(), flags.data()};

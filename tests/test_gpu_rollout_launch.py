@@ -1,5 +1,5 @@
 """GPU: rollout gather and GAE (K12) by launch geometry.  tests/test_gpu_rollout.py runs every case at N = 5 - two blocks of
-k_rollout_gather (a wave per env, four per block) and seven lanes of one wave of k_rollout_gae (an env per thread, 64 per block) -
+k_rollout_gather (a wave per env, four per block) and seven lanes of one wave of k_slot_fold<GaeFold> (an env per thread, 64 per block) -
 and at L <= 130 of AGX_ROLLOUT_LIMIT = 4096.  Here: GAE on synthetic arrays at N = 1, 63, 64, 65, 257 and every L mod 16 the short
 last register set can have, L = 4096, special floats, and the advantage against its DEFINITION in float64; the gather at N = 1, 4,
 9 and 257 and at L = 1000, 1024 and 4096 on tests/limit_cases.py's `deeproll` and `wide` (tests/test_limit_cases_cpu.py pins what

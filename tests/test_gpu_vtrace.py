@@ -96,7 +96,7 @@ def test_vtrace_equals_the_model_bit_for_bit(contexts, N):
 
 @pytest.mark.parametrize("N", vm.NS)
 def test_null_boot_buffer_reads_as_zero(contexts, N):
-    """d_boot_value = NULL (k_vtrace<false>): the model without a boot array, on ends bytes with and without the BOOT bit."""
+    """d_boot_value = NULL (k_slot_fold<VtraceFold, false>): the model without a boot array, on ends bytes with and without the BOOT bit."""
     ctx = contexts(N)
     for L in vm.LS:
         length, reward, ends, value, boot, rho, live = vm.case(N, L, 1000 * N + L)

@@ -1,4 +1,5 @@
-// The __host__ side of active-gym_amd/csrc/agx_vtrace_math.h - the very function k_vtrace folds every step with - on host arrays.
+// The __host__ side of active-gym_amd/csrc/agx_vtrace_math.h - the very function k_slot_fold<VtraceFold> folds every step with - on
+// host arrays.
 //
 //     vtrace_harness <file>            the tokens below, whitespace separated, read from a file
 //     vtrace_harness <token> ...       ... or given as arguments
@@ -8,60 +9,22 @@
 //          "vs_bits pg_adv_bits".  Floats travel as the decimal value of their 32-bit pattern.
 #include <cinttypes>
 #include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <string>
-#include <vector>
 
 #include "agx_vtrace_math.h"
-
-namespace {
-
-float from_bits(uint32_t u) {
-    float f;
-    memcpy(&f, &u, sizeof f);
-    return f;
-}
-uint32_t to_bits(float f) {
-    uint32_t u;
-    memcpy(&u, &f, sizeof u);
-    return u;
-}
-
-}  // namespace
+#include "harness_tokens.h"
 
 int main(int argc, char **argv) {
-    std::vector<std::string> tok;
-    if (argc == 2) {
-        FILE *f = fopen(argv[1], "r");
-        if (!f) {
-            fprintf(stderr, "cannot open %s\n", argv[1]);
-            return 2;
-        }
-        char buf[64];
-        while (fscanf(f, "%63s", buf) == 1) tok.emplace_back(buf);
-        fclose(f);
-    } else {
-        for (int i = 1; i < argc; ++i) tok.emplace_back(argv[i]);
-    }
-    size_t at = 0;
-    bool short_input = false;
-    auto next = [&]() -> int64_t {
-        if (at >= tok.size()) {
-            short_input = true;
-            return 0;
-        }
-        return strtoll(tok[at++].c_str(), nullptr, 10);
-    };
-    const int32_t N = (int32_t)next(), L = (int32_t)next();
+    Tokens in;
+    if (!in.read(argc, argv)) return 2;
+    const int32_t N = (int32_t)in.next(), L = (int32_t)in.next();
     agx::VtraceCoef c;
-    c.gamma = from_bits((uint32_t)next());
-    c.lambda = from_bits((uint32_t)next());
-    c.rho_bar = from_bits((uint32_t)next());
-    c.c_bar = from_bits((uint32_t)next());
-    c.pg_rho_bar = from_bits((uint32_t)next());
-    const bool has_boot = next() != 0;
-    if (short_input || N <= 0 || L < 1 || L > agx::kVtraceLimit) {
+    c.gamma = in.next_float();
+    c.lambda = in.next_float();
+    c.rho_bar = in.next_float();
+    c.c_bar = in.next_float();
+    c.pg_rho_bar = in.next_float();
+    const bool has_boot = in.next() != 0;
+    if (in.short_input || N <= 0 || L < 1 || L > agx::kVtraceLimit) {
         fprintf(stderr,
                 "usage: %s <file> | N L gamma_bits lambda_bits rho_bar_bits c_bar_bits pg_rho_bar_bits has_boot len[N] reward_bits[L*N] "
                 "ends[L*N] value_bits[L*N] rho_bits[L*N] [boot_bits[L*N]]\n",
@@ -72,13 +35,13 @@ int main(int argc, char **argv) {
     std::vector<int32_t> len(N);
     std::vector<float> reward(slots), value(slots), rho(slots), boot(has_boot ? slots : 0), vs(slots), pg(slots);
     std::vector<uint8_t> ends(slots);
-    for (auto &v : len) v = (int32_t)next();
-    for (auto &v : reward) v = from_bits((uint32_t)next());
-    for (auto &v : ends) v = (uint8_t)next();
-    for (auto &v : value) v = from_bits((uint32_t)next());
-    for (auto &v : rho) v = from_bits((uint32_t)next());
-    for (auto &v : boot) v = from_bits((uint32_t)next());
-    if (short_input || at != tok.size()) {
+    for (auto &v : len) v = (int32_t)in.next();
+    for (auto &v : reward) v = in.next_float();
+    for (auto &v : ends) v = (uint8_t)in.next();
+    for (auto &v : value) v = in.next_float();
+    for (auto &v : rho) v = in.next_float();
+    for (auto &v : boot) v = in.next_float();
+    if (!in.complete()) {
         fprintf(stderr, "%s: the arrays are incomplete or over-long\n", argv[0]);
         return 2;
     }

@@ -14,7 +14,7 @@ repetitions after --warmup.  Writes profiles/vtrace_bench.json.
 
     python tools/vtrace_bench.py [--iters 200] [--warmup 20] [--out profiles/vtrace_bench.json]
 
-The set depth of k_vtrace is a compile-time constant (AGX_VTRACE_AHEAD, 8).  To measure another one, build a library of its own
+The set depth of k_slot_fold<VtraceFold> is a compile-time constant (AGX_VTRACE_AHEAD, 8; GAE's is AGX_GAE_AHEAD, 16).  To measure another one, build a library of its own
 and select it through AGX_LIB; --set-depth only labels the result:
 
     python -c "import sys; sys.path.insert(0, 'active-gym_amd'); import build; \\
@@ -70,10 +70,10 @@ def main():
     def gae():
         roll.gae(batch, value, boot, gamma, lam, adv_out=adv, ret_out=ret)
 
-    def vtrace_no_boot():                         # k_vtrace<false>: one stream fewer, 21 bytes per slot (the values are not used)
+    def vtrace_no_boot():                         # k_slot_fold<VtraceFold, false>: one stream fewer, 21 bytes per slot (the values are not used)
         vt.returns(batch, value, None, rho, gamma, lam, *bars, vs_out=vs, pg_adv_out=pg)
 
-    def gae_no_boot():                            # k_rollout_gae<false>: 17 bytes per slot
+    def gae_no_boot():                            # k_slot_fold<GaeFold, false>: 17 bytes per slot
         roll.gae(batch, value, None, gamma, lam, adv_out=adv, ret_out=ret)
 
     ends, reward, live = batch["ends"], batch["reward"], batch["live"]
