@@ -7,15 +7,6 @@ namespace agx {
 // ---------------------------------------------------------------------------------------------
 // sensory action -> fov_loc   (fov_env.py:166-170,187-199; flexible: :270-271,300-324)
 // ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ double load_action(const void *p, int dt, size_t i) {
-    switch (dt) {
-        case AGX_DT_F32: return (double)static_cast<const float *>(p)[i];
-        case AGX_DT_F64: return static_cast<const double *>(p)[i];
-        case AGX_DT_I32: return (double)static_cast<const int32_t *>(p)[i];
-        default: return (double)static_cast<const int64_t *>(p)[i];
-    }
-}
-
 // np.rint(np.clip(x, lo, hi)).astype(int); NaN is normalised to lo (the reference is undefined there)
 __device__ __forceinline__ int clip_rint(double x, double lo, double hi) {
     x = fmax(x, lo);
@@ -163,22 +154,49 @@ __device__ __forceinline__ double action_value(int dt, uint32_t lo, uint32_t hi)
         default: return (double)(int64_t)(((uint64_t)hi << 32) | lo);
     }
 }
+// THE STATE RULE (include/agx.h, agx_set_fov_state): the stored state is whatever the caller set, so it is clamped AS IT IS READ -
+// fov_res to [1, obs], then fov_loc to [0, obs - fov_res] - and every window stays inside its env's frame.  compute_loc and
+// compute_flex_state are the only places that turn stored state + action into the state a kernel uses.
+__device__ __forceinline__ int clamp_state(int x, int lo, int hi) { return min(max(x, lo), hi); }
+// rint(clip(x, lo, hi)) kept in double: a relative delta (sas may be any lo <= hi, +-inf included) has no 32-bit limit
+__device__ __forceinline__ double clip_rint_d(double x, double lo, double hi) {
+    x = fmax(x, lo);
+    x = fmin(x, hi);
+    return rint(x);
+}
 __device__ __forceinline__ void compute_loc(const FovParams &p, const LocIn &in, int bound_r, int bound_c, int &r,
                                             int &c) {
-    r = in.r;
-    c = in.c;
+    r = clamp_state(in.r, 0, bound_r);
+    c = clamp_state(in.c, 0, bound_c);
     if (p.action) {
         const double ar = action_value(p.action_dt, in.w[0], in.w[1]);
         const double ac = action_value(p.action_dt, in.w[2], in.w[3]);
         if (p.relative) {
-            const int dr = clip_rint(ar, p.sas_lo, p.sas_hi);
-            const int dc = clip_rint(ac, p.sas_lo, p.sas_hi);
-            r = clip_rint((double)(r + dr), 0.0, (double)bound_r);
-            c = clip_rint((double)(c + dc), 0.0, (double)bound_c);
+            // the sum in double: exact for every int32 r and every double delta (|r| < 2^31: the sum rounds only far outside
+            // [0, bound], on the side it already is), where r + (int)delta would overflow
+            r = clip_rint((double)r + clip_rint_d(ar, p.sas_lo, p.sas_hi), 0.0, (double)bound_r);
+            c = clip_rint((double)c + clip_rint_d(ac, p.sas_lo, p.sas_hi), 0.0, (double)bound_c);
         } else {
             r = clip_rint(ar, 0.0, (double)bound_r);
             c = clip_rint(ac, 0.0, (double)bound_c);
         }
+    }
+}
+// The flexible env's whole state update (fov_env.py:300-324), for all five kernels that make one: res_old / type as loaded.
+// A sensory_action_type that is neither AGX_FOV_LOC nor AGX_FOV_RES acts as AGX_FOV_LOC.
+__device__ __forceinline__ void compute_flex_state(const FovParams &p, const LocIn &in, int2 res_old, int type, int oh, int ow,
+                                                   int &rh, int &rw, int &r, int &c) {
+    rh = clamp_state(res_old.x, 1, oh);
+    rw = clamp_state(res_old.y, 1, ow);
+    if (p.action && type == AGX_FOV_RES) {
+        r = clamp_state(in.r, 0, oh - rh);
+        c = clamp_state(in.c, 0, ow - rw);
+        rh = clip_rint(action_value(p.action_dt, in.w[0], in.w[1]), 1.0, (double)oh);
+        rw = clip_rint(action_value(p.action_dt, in.w[2], in.w[3]), 1.0, (double)ow);
+        r = min(r, oh - rh);
+        c = min(c, ow - rw);
+    } else {
+        compute_loc(p, in, oh - rh, ow - rw, r, c);
     }
 }
 __device__ __forceinline__ void next_loc(const FovParams &p, int n, int bound_r, int bound_c, int &r, int &c) {

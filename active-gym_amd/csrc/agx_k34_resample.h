@@ -92,17 +92,9 @@ __global__ __launch_bounds__(kThreads) void k_fovea_generic(GeomR g, FovParams p
     // ---- state update
     int rh = fh, rw = fw, r, c;
     if (flex) {
-        rh = p.res_in[2 * n];
-        rw = p.res_in[2 * n + 1];
+        const int2 res_old = *reinterpret_cast<const int2 *>(p.res_in + 2 * n);
         const int type = (p.action && p.action_type) ? p.action_type[n] : AGX_FOV_LOC;
-        if (p.action && type == AGX_FOV_RES) {
-            rh = clip_rint(load_action(p.action, p.action_dt, 2 * (size_t)n), 1.0, (double)oh);
-            rw = clip_rint(load_action(p.action, p.action_dt, 2 * (size_t)n + 1), 1.0, (double)ow);
-            r = clip_rint((double)p.loc_in[2 * n], 0.0, (double)(oh - rh));
-            c = clip_rint((double)p.loc_in[2 * n + 1], 0.0, (double)(ow - rw));
-        } else {
-            next_loc(p, n, oh - rh, ow - rw, r, c);
-        }
+        compute_flex_state(p, load_loc_inputs(p, n), res_old, type, oh, ow, rh, rw, r, c);
     } else {
         next_loc(p, n, oh - fh, ow - fw, r, c);
     }
@@ -553,15 +545,8 @@ __global__ __launch_bounds__(kThreads) void k_fovea_flexible2(FlexParams g, FovP
     const int head = p.head[n];
     lut[tid] = unit((uint32_t)tid);
     // ---- state update (fov_env.py:300-324)
-    int rh = res_old.x, rw = res_old.y, r, c;
-    if (p.action && type == AGX_FOV_RES) {
-        rh = clip_rint(action_value(p.action_dt, lin.w[0], lin.w[1]), 1.0, (double)oh);
-        rw = clip_rint(action_value(p.action_dt, lin.w[2], lin.w[3]), 1.0, (double)ow);
-        r = clip_rint((double)lin.r, 0.0, (double)(oh - rh));
-        c = clip_rint((double)lin.c, 0.0, (double)(ow - rw));
-    } else {
-        compute_loc(p, lin, oh - rh, ow - rw, r, c);
-    }
+    int rh, rw, r, c;
+    compute_flex_state(p, lin, res_old, type, oh, ow, rh, rw, r, c);
     int j = sl - head;
     if (j < 0) j += p.fs;
     if (q_ == 0 && tid == 0) {

@@ -132,16 +132,9 @@ __global__ __launch_bounds__(kThreads) AGX_K4_OCC void k_fovea_flexible3(G g, Fl
     const LocIn lin = load_flex_inputs_scalar(p, n, head, res_old, type);     // through the scalar cache: a shorter first hop
     const uint32_t *fsrc = reinterpret_cast<const uint32_t *>(p.ring + (((size_t)n * p.fs + sl) * NC + ch) * (size_t)fbytes);
 
-    // ---- state update (fov_env.py:300-324); res from agx_set_fov_state is clamped for memory safety only
-    int rh = min(max(res_old.x, 1), oh), rw = min(max(res_old.y, 1), ow), r, c;
-    if (p.action && type == AGX_FOV_RES) {
-        rh = clip_rint(action_value(p.action_dt, lin.w[0], lin.w[1]), 1.0, (double)oh);
-        rw = clip_rint(action_value(p.action_dt, lin.w[2], lin.w[3]), 1.0, (double)ow);
-        r = clip_rint((double)lin.r, 0.0, (double)(oh - rh));
-        c = clip_rint((double)lin.c, 0.0, (double)(ow - rw));
-    } else {
-        compute_loc(p, lin, oh - rh, ow - rw, r, c);
-    }
+    // ---- state update (fov_env.py:300-324); the stored state is clamped as it is read (agx_fov_common.h)
+    int rh, rw, r, c;
+    compute_flex_state(p, lin, res_old, type, oh, ow, rh, rw, r, c);
     // workgroup-uniform from here on: scalar registers, scalar branches, scalar trip counts
     rh = __builtin_amdgcn_readfirstlane(rh);
     rw = __builtin_amdgcn_readfirstlane(rw);

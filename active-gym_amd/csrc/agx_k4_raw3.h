@@ -63,15 +63,8 @@ __device__ __forceinline__ void flex_state_scan_block(const FlexScanParams &q, c
         const LocIn lin = load_loc_inputs(p, n);
         const int2 res_old = *reinterpret_cast<const int2 *>(p.res_in + 2 * n);
         const int type = (p.action && p.action_type) ? p.action_type[n] : AGX_FOV_LOC;
-        int rh = min(max(res_old.x, 1), q.oh), rw = min(max(res_old.y, 1), q.ow), r, c;
-        if (p.action && type == AGX_FOV_RES) {
-            rh = clip_rint(action_value(p.action_dt, lin.w[0], lin.w[1]), 1.0, (double)q.oh);
-            rw = clip_rint(action_value(p.action_dt, lin.w[2], lin.w[3]), 1.0, (double)q.ow);
-            r = clip_rint((double)lin.r, 0.0, (double)(q.oh - rh));
-            c = clip_rint((double)lin.c, 0.0, (double)(q.ow - rw));
-        } else {
-            compute_loc(p, lin, q.oh - rh, q.ow - rw, r, c);
-        }
+        int rh, rw, r, c;
+        compute_flex_state(p, lin, res_old, type, q.oh, q.ow, rh, rw, r, c);
         *reinterpret_cast<int2 *>(p.loc_out + 2 * n) = make_int2(r, c);
         *reinterpret_cast<int2 *>(p.res_out + 2 * n) = make_int2(rh, rw);
         if (p.user_loc) *reinterpret_cast<int2 *>(p.user_loc + 2 * n) = make_int2(r, c);
@@ -164,15 +157,7 @@ __global__ __launch_bounds__(kThreads) void k_fovea_flexible_raw3(G g, FlexRawPa
         int type;
         int2 res_old;
         const LocIn lin = load_flex_inputs_scalar(p, n, head, res_old, type);
-        rh = min(max(res_old.x, 1), oh), rw = min(max(res_old.y, 1), ow);
-        if (p.action && type == AGX_FOV_RES) {
-            rh = clip_rint(action_value(p.action_dt, lin.w[0], lin.w[1]), 1.0, (double)oh);
-            rw = clip_rint(action_value(p.action_dt, lin.w[2], lin.w[3]), 1.0, (double)ow);
-            r = clip_rint((double)lin.r, 0.0, (double)(oh - rh));
-            c = clip_rint((double)lin.c, 0.0, (double)(ow - rw));
-        } else {
-            compute_loc(p, lin, oh - rh, ow - rw, r, c);
-        }
+        compute_flex_state(p, lin, res_old, type, oh, ow, rh, rw, r, c);
         rh = __builtin_amdgcn_readfirstlane(rh);
         rw = __builtin_amdgcn_readfirstlane(rw);
         r = __builtin_amdgcn_readfirstlane(r);

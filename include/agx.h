@@ -223,6 +223,11 @@ AGX_API int agx_set_stack_u8(agx_ctx *ctx, const uint8_t *d_in, void *stream);
  * whose mask byte is non-zero (d_mask == NULL: all envs). */
 AGX_API int agx_fovea_reset(agx_ctx *ctx, const uint8_t *d_mask, void *stream);
 AGX_API int agx_get_fov_state(agx_ctx *ctx, int32_t *d_fov_loc /*[N][2]*/, int32_t *d_fov_res /*[N][2], may be NULL*/, void *stream);
+/* agx_set_fov_state copies the caller's values as they are (device pointers, enqueue-only: nothing is checked on the host) and
+ * agx_get_fov_state returns what is stored.  CLAMP ON READ: every agx_fovea_* / agx_step_* call clamps the state as it reads it -
+ * fov_res to [1, obs] (flexible kind; the other kinds use fov_size), then fov_loc to [0, obs - fov_res] - before the action is
+ * applied, so a set state outside the frame never moves a window outside it; the state the call stores and returns is the
+ * clamped, updated one.  An env the call's mask leaves out keeps its stored state as it is. */
 AGX_API int agx_set_fov_state(agx_ctx *ctx, const int32_t *d_fov_loc, const int32_t *d_fov_res /*may be NULL*/, void *stream);
 
 /* ---- K2: FixedFovealEnv._fov_step (fov_env.py:166-203) ------------------
@@ -231,6 +236,13 @@ AGX_API int agx_set_fov_state(agx_ctx *ctx, const int32_t *d_fov_loc, const int3
  *   absolute: fov_loc = rint(clip(a, 0, obs - fov))
  *   relative: fov_loc = rint(clip(fov_loc + rint(clip(a, sas_lo, sas_hi)), 0, obs - fov))
  * then crop / mask-out paste / bilinear resize per out_mode.
+ * The same rules hold for every agx_fovea_* / agx_step_* entry point:
+ *   - the fov_loc (and fov_res) that is read is clamped first (CLAMP ON READ, agx_set_fov_state), also when d_action is NULL;
+ *   - every clip is fmin(fmax(x, lo), hi) in double: a NaN action element goes to the LOWER bound of the clip it meets (0 for
+ *     an absolute location, sas_lo for a relative delta, 1 for a resolution); +-inf and huge values clip like any other;
+ *   - the action element is widened to double exactly (f32, f64, i32) or rounded to nearest (i64 beyond 2^53), never narrowed;
+ *   - the relative sum fov_loc + delta is formed in double, without a 32-bit limit: any sas_lo <= sas_hi, +-inf included, is
+ *     exact.
  * d_obs     : the context's AGX_OBS_* element type (f32 by default), shape per agx_obs_shape
  * d_fov_loc : i32 [N][2] out, may be NULL          (info["fov_loc"], fov_env.py:217)
  * d_mask    : u8 [N] or NULL; envs with 0 are left untouched (state and d_obs rows). */
@@ -252,11 +264,12 @@ AGX_API int agx_fovea_peripheral(agx_ctx *ctx, const void *d_action, int action_
                          float *d_obs, int32_t *d_fov_loc, void *stream);
 
 /* ---- K4: FlexibleFovealEnv._fov_step (fov_env.py:270-330) ---------------
- * d_action_type: i32 [N] AGX_FOV_LOC / AGX_FOV_RES (NULL = all FOV_LOC).
+ * d_action_type: i32 [N] AGX_FOV_LOC / AGX_FOV_RES (NULL = all FOV_LOC).  Any value that is not AGX_FOV_RES acts as
+ *   AGX_FOV_LOC (the reference raises NotImplementedError; a device kernel cannot).
  *   FOV_RES: fov_res = action (the reference stores it unclipped and only
  *   integer values inside [1, obs] are usable there; this ABI rints float
- *   input and clamps to [1, obs] — documented normalisation), then fov_loc is
- *   re-clipped to obs - fov_res.
+ *   input and clamps to [1, obs] — documented normalisation; NaN gives 1), then
+ *   fov_loc (clamped on read to the OLD fov_res, agx_set_fov_state) is re-clipped to obs - fov_res.
  * iff fov_res rows > fov_size rows: crop is resized to fov_size and back
  * (fov_env.py:276-287), then mask / resize-to-obs / raw per out_mode. */
 AGX_API int agx_fovea_flexible(agx_ctx *ctx, const void *d_action, int action_dtype, const int32_t *d_action_type,
