@@ -188,6 +188,14 @@ class FrameHistory(Owner):
             log = self._samplers[key] = BehaviourLog(self, width)
         return log
 
+    def minibatcher(self, rollout, seed: int = 0):
+        """The one minibatch.Minibatcher of this seed on this history, made at first use (``rollout``: the Rollout it is made on)."""
+        key = ("minibatch", int(seed))
+        mb = self._samplers.get(key)
+        if mb is None:
+            mb = self._samplers[key] = rollout.minibatcher(seed)
+        return mb
+
     def transition_obs(self, read, env, index, next_index, shift=None) -> dict:
         """The observation part of a transition batch through ``read`` (``self.observe`` or a GlimpseMemory's): obs, next_obs
         and, on a fixed pipeline, fov_loc, next_fov_loc.  ``shift``: the augment.RandomShift whose ``observe`` ``read`` is - two

@@ -122,6 +122,12 @@ class Rollout:
         self._check(self._lib.agx_rollout_gae(self.history.handle, L, *args, float(gamma), float(lam), pa, pt, self.pipe._stream()))
         return adv_out, ret_out
 
+    def minibatcher(self, seed: int = 0):
+        """A minibatch.Minibatcher on this rollout's history: the device-side lists of a batch's LIVE and BOOT slots and their
+        seeded shuffles - what ``flat`` and ``boot_rows`` give, without their synchronisation."""
+        from .minibatch import Minibatcher
+        return Minibatcher(self, seed)
+
     def flat(self, batch: dict, which: str = "obs"):
         """(env i32 [M], index i64 [M]) of the M live slots, in [L, N] order: the samples of ``FrameHistory.observe`` for the
         observations the actions were taken on (``which = "obs"``) or the ones the steps returned (``"next"``).  A minibatch of

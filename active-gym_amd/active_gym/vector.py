@@ -506,6 +506,71 @@ class AtariVecEnv:
         mu's log-probability being what ``env.behaviour_log()`` kept.  Needs ``step_log``: ValueError otherwise."""
         return self._rollout("rollout_vtrace", vtrace=True).returns(batch, value, boot_value, rho, gamma, lam, rho_bar, c_bar, pg_rho_bar)
 
+    def _minibatcher(self, who: str, seed: Optional[int]):
+        """The env's minibatch.Minibatcher of this seed (None: ``args.seed``), cached on the history; ValueError without a step log."""
+        roll = self._rollout(who)
+        seed = int(getattr(self.args, "seed", 0) or 0) if seed is None else int(seed)
+        return self.history.minibatcher(roll, seed)
+
+    def _with_payload(self, batch: dict) -> dict:
+        """A ``rollout_batch`` with its actions put back into one payload u8 [L, N, W], as the step log holds them."""
+        parts = [batch["motor_action"].view(torch.uint8).reshape(*batch["motor_action"].shape, 4)]
+        if self.kind == "fixed":
+            parts.append(batch["sensory_action"].view(torch.uint8).reshape(*batch["motor_action"].shape, 8))
+        return dict(batch, payload=torch.cat(parts, -1))
+
+    def _split_payload(self, rows: dict) -> dict:
+        words = rows.pop("payload").view(torch.int32)
+        rows["motor_action"] = words[:, 0].contiguous()
+        if self.kind == "fixed":
+            rows["sensory_action"] = words[:, 1:3].contiguous().view(torch.float32)
+        return rows
+
+    def rollout_boot(self, batch: dict, capacity: Optional[int] = None, seed: Optional[int] = None) -> dict:
+        """The slots of a ``rollout_batch`` whose return bootstraps (BOOT), in list order and without a shuffle, at the fixed
+        shape ``[capacity]`` (default ``2 * N``): ``minibatch.Minibatcher.take(batch, 0, capacity, "boot", permute=False)`` plus
+        ``total``, the device i32 [1] number of such slots - the host never waits for it, so an overflow (``total > capacity``)
+        is visible later.  The capture-safe replacement for ``Rollout.boot_rows``::
+
+            rows = env.rollout_boot(batch)
+            obs = env.history.observe(rows["env"], rows["next_index"])[0]         # 1. observe the list (rows past it: valid = 0)
+            v = critic(obs)                                                        # 2. evaluate the critic
+            boot_value = torch.zeros_like(batch["reward"])
+            env.rollout_scatter(rows, v, boot_value)                               # 3. scatter into a zeroed boot_value
+
+        Needs ``step_log``: ValueError otherwise."""
+        from .minibatch import check_minibatch_size
+        mb = self._minibatcher("rollout_boot", seed)
+        _, capacity = check_minibatch_size(2 * self.num_envs if capacity is None else capacity)
+        total = mb.select(batch, "boot")
+        rows = mb.take(self._with_payload(batch), 0, capacity, "boot", permute=False)
+        rows["total"] = total
+        return self._split_payload(rows)
+
+    def rollout_scatter(self, rows: dict, values: torch.Tensor, dst: torch.Tensor, seed: Optional[int] = None) -> torch.Tensor:
+        """``minibatch.Minibatcher.scatter``: ``values`` (f32 [S]) of the valid ``rows`` into ``dst`` (f32 [L, N]) at their slots."""
+        return self._minibatcher("rollout_scatter", seed).scatter(rows, values, dst)
+
+    def rollout_minibatches(self, batch: dict, size: int, streams=None, seed: Optional[int] = None):
+        """One epoch over the live slots of a ``rollout_batch``, freshly shuffled on the device: a generator of
+        ``ceil(L * N / size)`` dicts of ``size`` rows each - ``slot``, ``env``, ``obs_index``, ``next_index``, ``valid``,
+        ``motor_action`` (i32 [size]) and, on a fixed env, ``sensory_action`` (f32 [size, 2]), and one f32 [size] entry per name
+        in ``streams`` (a dict name -> f32 [L, N] such as adv / ret / value / logp, or names of entries of ``batch``).  The number
+        of minibatches is that of a full rollout, so it is no data: rows past the live slots wrap to real samples with
+        ``valid = 0``, and a learner multiplies its per-row loss by ``valid``.  Every live slot is in exactly one row with
+        ``valid = 1``.  Nothing synchronises.  Needs ``step_log``: ValueError otherwise."""
+        from .minibatch import check_epoch_size, check_streams
+        mb = self._minibatcher("rollout_minibatches", seed)
+        size = check_epoch_size(size)
+        streams = check_streams(streams, batch)
+        return self._minibatch_epoch(mb, self._with_payload(batch), size, streams)
+
+    def _minibatch_epoch(self, mb, batch, size, streams):
+        cells = int(batch["ends"].shape[0]) * self.num_envs
+        mb.select(batch, "live")
+        for first in range(0, cells, size):
+            yield self._split_payload(mb.take(batch, first, size, "live", True, streams))
+
     def behaviour_log(self, width: int = 1):
         """A vtrace.BehaviourLog on the env's frame history, cached per width: ``write(info["history_index"], logp)`` at every
         act, ``read(batch["obs_index"])`` after ``rollout_batch``.  Needs ``history_len`` > 0: ValueError otherwise."""

@@ -17,6 +17,7 @@
 //   k_sequence_gather / k_sequence_observe  K11  sequence replay: L consecutive steps of one episode per sample, padded with zeros
 //   k_rollout_gather / k_slot_fold<GaeFold>  K12  on-policy rollouts: the last L transitions of every env, cut at episode ends, and GAE
 //   k_slot_fold<VtraceFold>  K13 V-trace targets and policy-gradient advantages over a gathered rollout, for actor-learner training
+//   k_mb_count / k_mb_scan / k_mb_take / k_mb_scatter  K15  minibatches on a gathered rollout: its LIVE / BOOT slot lists, shuffled
 //
 // The fixed fovea's phases are stated once in agx_fixed_phases.h (K2, K5, K6, K10, K11 run them).  The three kernels that re-create
 // observation planes from history rows - k_history_observe, k_history_observe_shifted, k_sequence_observe - are one body,
@@ -49,6 +50,7 @@
 #include "agx_k4_flex3.h"
 #include "agx_k4_raw3.h"
 #include "agx_k14_step_packed.h"
+#include "agx_k15_minibatch.h"
 #ifdef AGX_EXPERIMENTS
 #include "experiments/agx_experiments.h"   // measured dead ends: tools/ and the variants test only, never in libagx.so
 #include "experiments/agx_packed_wave.h"
