@@ -471,6 +471,33 @@ class AtariVecEnv:
             out["weight"], out["priority"] = sampler.importance(beta), sampler.weight
         return out
 
+    def sequence_retrace(self, batch: dict, q: torch.Tensor, v: torch.Tensor, c: torch.Tensor, boot: Optional[torch.Tensor] = None,
+                         out: Optional[dict] = None, time_major: bool = False) -> dict:
+        """The Retrace-family Q-return over a ``sequence_batch(nstep=1)`` -> dict of ``target``, ``td`` (f32) and ``valid`` (u8),
+        [B, length]: ``retrace.Retrace(env.steplog).targets(...)``, for an off-policy recurrent learner.  The whole recipe::
+
+            batch = env.sequence_batch(B, L, nstep=1)                             # ret = the step's reward, steps = 1 where a row exists
+            q_all, pi = learner(batch["obs"])                                      # [B, L, A]: the Q values and the target policy
+            a = batch["motor_action"].long()[..., None]
+            q, v = q_all.gather(-1, a)[..., 0], (pi * q_all).sum(-1)
+            last = batch["next_index"][:, -1]                                      # -1 where the sequence stops short: boot is not read there
+            boot_obs = env.history.observe(batch["env"], last)[0]                  # the observation behind the last step
+            q_b, pi_b = learner.single(boot_obs)
+            boot = (pi_b * q_b).sum(-1)
+            at = batch["index"][:, None] + torch.arange(L, device=device)         # step l is the env-step (env, index + l)
+            logp_mu = env.behaviour_log().read(at.reshape(-1), batch["env"].repeat_interleave(L)).reshape(B, L)     # mu, as written at every act
+            c = retrace.coefficients(pi.log().gather(-1, a)[..., 0], logp_mu, lam=0.95, kind="retrace")
+            out = env.sequence_retrace(batch, q, v, c, boot)
+            loss = ((q - out["target"].detach()) ** 2 * out["valid"]).sum() / out["valid"].sum().clamp(min=1)
+            priority = sequence.mixed_priority(out["td"].abs(), batch["live"])     # then env.update_priorities(batch, priority)
+
+        ``kind="qlambda"`` and ``"tree"`` need no behaviour policy.  ``valid`` is ``live & (steps == 1)``; every other step is 0
+        in all three outputs.  ``out``: the dict of an earlier call, written in place.  Needs ``step_log``: ValueError otherwise."""
+        if self.steplog is None:
+            raise ValueError("sequence_retrace needs a step log (AtariEnvArgs.step_log = True, history_len > 0)")
+        from .retrace import Retrace
+        return Retrace(self.steplog).targets(batch, q, v, c, boot, out, time_major)
+
     def _rollout(self, who: str, vtrace: bool = False):
         """The env's rollout.Rollout (vtrace: vtrace.VTrace) on its step log; ValueError without one."""
         if self.steplog is None:

@@ -18,6 +18,7 @@
 //   k_rollout_gather / k_slot_fold<GaeFold>  K12  on-policy rollouts: the last L transitions of every env, cut at episode ends, and GAE
 //   k_slot_fold<VtraceFold>  K13 V-trace targets and policy-gradient advantages over a gathered rollout, for actor-learner training
 //   k_mb_count / k_mb_scan / k_mb_take / k_mb_scatter  K15  minibatches on a gathered rollout: its LIVE / BOOT slot lists, shuffled
+//   k_retrace_direct  K16  Retrace-family Q-returns folded backward along the sequences of a sequence-replay batch
 //
 // The fixed fovea's phases are stated once in agx_fixed_phases.h (K2, K5, K6, K10, K11 run them).  The three kernels that re-create
 // observation planes from history rows - k_history_observe, k_history_observe_shifted, k_sequence_observe - are one body,
@@ -51,7 +52,9 @@
 #include "agx_k4_raw3.h"
 #include "agx_k14_step_packed.h"
 #include "agx_k15_minibatch.h"
+#include "agx_k16_retrace.h"
 #ifdef AGX_EXPERIMENTS
 #include "experiments/agx_experiments.h"   // measured dead ends: tools/ and the variants test only, never in libagx.so
 #include "experiments/agx_packed_wave.h"
+#include "experiments/agx_retrace_tiled.h"
 #endif
