@@ -20,11 +20,43 @@
 #include "agx_host_tables.h"
 #include "agx_plan.h"
 #include "agx_device_guard.h"
+#include "agx_resources.h"
 #include "agx_range.h"
 
 using namespace agx;
 
+namespace {
+
+struct HipDeviceApi {
+    static int get(int *dev) { return hipGetDevice(dev) == hipSuccess ? 0 : 1; }
+    static int set(int dev) { return hipSetDevice(dev) == hipSuccess ? 0 : 1; }
+};
+using DeviceGuard = agx::DeviceGuardT<HipDeviceApi>;      // agx_device_guard.h (unit-tested with a mocked runtime)
+
+// The runtime behind agx_resources.h: the one place in csrc/ that names these calls.  Everything a handle holds comes from
+// the Resources member of its struct and goes back when the struct is deleted.
+struct HipResourceApi : HipDeviceApi {
+    using Error = hipError_t;
+    static Error device_alloc(void **p, size_t bytes) { return hipMalloc(p, bytes); }
+    static void device_free(void *p) { (void)hipFree(p); }
+    static Error pinned_alloc(void **p, size_t bytes) { return hipHostMalloc(p, bytes, hipHostMallocDefault); }
+    static void pinned_free(void *p) { (void)hipHostFree(p); }
+    static Error event_create(void **e, unsigned flags) { return hipEventCreateWithFlags(reinterpret_cast<hipEvent_t *>(e), flags); }
+    static void event_destroy(void *e) { (void)hipEventDestroy(static_cast<hipEvent_t>(e)); }
+    static Error stream_create(void **s, unsigned flags) { return hipStreamCreateWithFlags(reinterpret_cast<hipStream_t *>(s), flags); }
+    static Error stream_create_priority(void **s, unsigned flags, int priority) {
+        return hipStreamCreateWithPriority(reinterpret_cast<hipStream_t *>(s), flags, priority);
+    }
+    static void stream_destroy(void *s) { (void)hipStreamDestroy(static_cast<hipStream_t>(s)); }
+};
+using Resources = agx::ResourcesT<HipResourceApi>;        // agx_resources.h (unit-tested with a mocked runtime)
+
+}  // namespace
+
 struct agx_ctx {
+    explicit agx_ctx(int device) : own(device) {}
+    Resources own;             // owns every device allocation below (and the experiments build's streams and events): the typed
+                               // pointers the launches read are views into it
     agx_config cfg;            // cfg.out_mode holds the mode only (AGX_OUT_*); its element type bits are obs_type
     int obs_type = AGX_OBS_F32;   // AGX_OBS_F32 | AGX_OBS_BF16 | AGX_OBS_F16
     int planes = 1;               // planes per frame: 1 gray, 3 colour (AGX_FRAME_RGB); the ring holds planes * fs per env
@@ -58,16 +90,16 @@ struct agx_ctx {
     // K4 raw-crop / mask-out / packed forms (k_fovea_flexible_raw3, agx_k4_raw3.h)
     FlexRawParams fr{};
     int64_t *pack_local = nullptr;   // agx_fovea_flexible_packed: [N] block-local exclusive offsets, [ceil(N/256)] block totals
-    int64_t *pack_block = nullptr;   // (both allocated in agx_create for flexible raw-crop contexts: no allocation in a step call)
+    int64_t *pack_block = nullptr;   // (both made in agx_create for flexible raw-crop contexts: no allocation in a step call)
     // K3 tuned form 3 (k_fovea_peripheral3)
     Per3Params p3{};
     // What runs (agx_plan.h), computed once in agx_create: the fovea launch of the context's kind, and the K1 launch of each
     // screen layout (K1Layout) at the band height in force for it
     FovPlan plan;
     K1Launch k1l[4];
-    std::vector<void *> owned;    // further device allocations freed by agx_destroy
 #ifdef AGX_EXPERIMENTS
     // split step (agx_step_fixed): env-range parts 1.. run on these internal streams, forked from / joined to the caller's
+    // (made on first use, from own)
     hipStream_t aux[3] = {nullptr, nullptr, nullptr};
     hipEvent_t ev_fork = nullptr, ev_join[3] = {nullptr, nullptr, nullptr};
 #endif
@@ -139,30 +171,17 @@ int fail(agx_ctx *ctx, int code, const char *fmt, ...) {
         if (e_ != hipSuccess) return fail((ctx), AGX_E_HIP, "%s: %s", #expr, hipGetErrorString(e_)); \
     } while (0)
 
-struct HipDeviceApi {
-    static int get(int *dev) { return hipGetDevice(dev) == hipSuccess ? 0 : 1; }
-    static int set(int dev) { return hipSetDevice(dev) == hipSuccess ? 0 : 1; }
-};
-using DeviceGuard = agx::DeviceGuardT<HipDeviceApi>;      // agx_device_guard.h (unit-tested with a mocked runtime)
-
 inline hipStream_t S(void *s) { return static_cast<hipStream_t>(s); }
 
-template <class T>
-int upload(agx_ctx *ctx, T **dptr, const std::vector<T> &h) {
-    AGX_HIP(ctx, hipMalloc(reinterpret_cast<void **>(dptr), h.size() * sizeof(T)));
-    AGX_HIP(ctx, hipMemcpy(*dptr, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice));
-    return AGX_OK;
-}
-
-template <class T>
-int upload_owned(agx_ctx *ctx, const T **dptr, const std::vector<T> &h) {
+// a host table as a device allocation of the context (P: T or const T, as the launch parameters spell the field)
+template <class P, class T>
+int upload(agx_ctx *ctx, P **dptr, const std::vector<T> &h) {
+    static_assert(std::is_same<typename std::remove_const<P>::type, T>::value, "the field's element type is the table's");
     T *d = nullptr;
-    const int rc = upload(ctx, &d, h);
-    if (rc == AGX_OK) {
-        ctx->owned.push_back(d);
-        *dptr = d;
-    }
-    return rc;
+    AGX_HIP(ctx, ctx->own.device_mem(&d, h.size() * sizeof(T)));
+    AGX_HIP(ctx, hipMemcpy(d, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice));
+    *dptr = d;
+    return AGX_OK;
 }
 
 bool has_fovea(const agx_config &c) { return c.kind != AGX_KIND_BASE; }
@@ -422,28 +441,11 @@ int agx_device_pci_bus_id(int device, char *buf, int len) {
 int agx_destroy(agx_ctx *ctx) {
     if (!ctx) return AGX_OK;
     DeviceGuard g(ctx->cfg.device);
-    void *ptrs[] = {ctx->ring, ctx->head[0], ctx->head[1], ctx->loc[0], ctx->loc[1], ctx->res[0], ctx->res[1],
-                    ctx->in_xtab, ctx->in_ytab, ctx->in_ytab_c, ctx->in_xtab12, ctx->in_ytab12, ctx->fx_xtab, ctx->fx_ytab,
-                    ctx->per_ln[0], ctx->per_ln[1], ctx->per_ln[2], ctx->per_ln[3],
-                    ctx->per_w[0], ctx->per_w[1], ctx->per_w[2], ctx->per_w[3],
-                    ctx->flex_ln[0], ctx->flex_ln[1], ctx->flex_ln[2], ctx->flex_ln[3], ctx->flex_ln[4], ctx->flex_ln[5],
-                    ctx->flex_w[0], ctx->flex_w[1], ctx->flex_w[2], ctx->flex_w[3], ctx->flex_w[4], ctx->flex_w[5],
-                    ctx->flex_meta[0], ctx->flex_meta[1], ctx->flex_meta[2], ctx->flex_meta[3], ctx->flex_meta[4],
-                    ctx->flex_meta[5]};
-    for (void *p : ptrs)
-        if (p) (void)hipFree(p);
-    for (void *p : ctx->owned)
-        if (p) (void)hipFree(p);
-#ifdef AGX_EXPERIMENTS
-    for (hipStream_t st : ctx->aux)
-        if (st) (void)hipStreamDestroy(st);
-    if (ctx->ev_fork) (void)hipEventDestroy(ctx->ev_fork);
-    for (hipEvent_t e : ctx->ev_join)
-        if (e) (void)hipEventDestroy(e);
-#endif
     delete ctx;
     return AGX_OK;
 }
+
+static int ctx_build(agx_ctx *ctx);
 
 int agx_create(const agx_config *cfg, agx_ctx **out) {
     if (!cfg || !out) return fail(nullptr, AGX_E_INVALID, "agx_create: null argument");
@@ -498,7 +500,7 @@ int agx_create(const agx_config *cfg, agx_ctx **out) {
         return fail(nullptr, AGX_E_HIP, "no HIP device: libagx has no CPU path");
     if (c.device < 0 || c.device >= ndev) return fail(nullptr, AGX_E_INVALID, "device %d out of range (%d visible)", c.device, ndev);
 
-    agx_ctx *ctx = new (std::nothrow) agx_ctx;
+    agx_ctx *ctx = new (std::nothrow) agx_ctx(c.device);
     if (!ctx) return fail(nullptr, AGX_E_NOMEM, "out of host memory");
     ctx->cfg = c;
     ctx->obs_type = obs_type;
@@ -520,26 +522,29 @@ int agx_create(const agx_config *cfg, agx_ctx **out) {
     ctx->tune.packed_wave = env_int("AGX_PACKED_WAVE");
 #endif
     DeviceGuard g(c.device);
-    int rc = AGX_OK;
-    auto bail = [&](int code) {
+    const int rc = ctx_build(ctx);
+    if (rc != AGX_OK) {                 // whatever the context holds by now goes back with it
         g_create_err = ctx->err;
-        agx_destroy(ctx);
-        return code;
-    };
+        delete ctx;
+        return rc;
+    }
+    *out = ctx;
+    return AGX_OK;
+}
+
+// What agx_create allocates and uploads for a checked configuration (the plans ride along: they read the host tables).  Any
+// failure leaves its message in ctx->err and returns; agx_create deletes the context, which gives back whatever was made.
+static int ctx_build(agx_ctx *ctx) {
+    const agx_config &c = ctx->cfg;
+    const Knobs &tune = ctx->tune;      // the five shipped knobs: what the plans read
+    const int planes = ctx->planes;
+    int rc = AGX_OK;
     const size_t N = c.num_envs, fsz = (size_t)c.obs_h * c.obs_w;
-#define TRY(expr)                                  \
-    do {                                           \
-        hipError_t e_ = (expr);                    \
-        if (e_ != hipSuccess) {                    \
-            fail(ctx, AGX_E_HIP, "%s: %s", #expr, hipGetErrorString(e_)); \
-            return bail(AGX_E_HIP);                \
-        }                                          \
-    } while (0)
-    TRY(hipMalloc(reinterpret_cast<void **>(&ctx->ring), N * c.frame_stack * planes * fsz));
-    TRY(hipMemset(ctx->ring, 0, N * c.frame_stack * planes * fsz));
+    AGX_HIP(ctx, ctx->own.device_mem(&ctx->ring, N * c.frame_stack * planes * fsz));
+    AGX_HIP(ctx, hipMemset(ctx->ring, 0, N * c.frame_stack * planes * fsz));
     for (int b = 0; b < 2; ++b) {
-        TRY(hipMalloc(reinterpret_cast<void **>(&ctx->head[b]), N * sizeof(int32_t)));
-        TRY(hipMemset(ctx->head[b], 0, N * sizeof(int32_t)));
+        AGX_HIP(ctx, ctx->own.device_mem(&ctx->head[b], N * sizeof(int32_t)));
+        AGX_HIP(ctx, hipMemset(ctx->head[b], 0, N * sizeof(int32_t)));
     }
     // K1 tables and plan (only meaningful for square obs; built anyway, agx_ingest checks): build_k1, agx_host_tables.h
     {
@@ -558,11 +563,11 @@ int agx_create(const agx_config *cfg, agx_ctx **out) {
             ytc[i] = make_int4(k1.py0[i], k1.py1[i], k1.b0[i], k1.b1[i]);
             yt12[i] = make_int2(k1.b0[i] << 8, k1.b1[i] << 8);
         }
-        if ((rc = upload(ctx, &ctx->in_ytab_c, ytc)) != AGX_OK) return bail(rc);
-        if ((rc = upload(ctx, &ctx->in_xtab, xt)) != AGX_OK) return bail(rc);
-        if ((rc = upload(ctx, &ctx->in_ytab, yt)) != AGX_OK) return bail(rc);
-        if ((rc = upload(ctx, &ctx->in_xtab12, xt12)) != AGX_OK) return bail(rc);
-        if ((rc = upload(ctx, &ctx->in_ytab12, yt12)) != AGX_OK) return bail(rc);
+        if ((rc = upload(ctx, &ctx->in_ytab_c, ytc)) != AGX_OK) return rc;
+        if ((rc = upload(ctx, &ctx->in_xtab, xt)) != AGX_OK) return rc;
+        if ((rc = upload(ctx, &ctx->in_ytab, yt)) != AGX_OK) return rc;
+        if ((rc = upload(ctx, &ctx->in_xtab12, xt12)) != AGX_OK) return rc;
+        if ((rc = upload(ctx, &ctx->in_ytab12, yt12)) != AGX_OK) return rc;
         // the RGB whole-screen ingest: 128-thread workgroups give 16 independent workgroups per CU whose load / compute
         // phases interleave (AGX_INGEST_T tunes; 8 WGs/CU whatever T: 256 fills the wave slots), fewer rows per band
         // (AGX_INGEST_BAND_ROWS).  Both knobs are 0 in the shipped library: band_rows is then the plan's.
@@ -582,11 +587,9 @@ int agx_create(const agx_config *cfg, agx_ctx **out) {
         // _init_fov_loc: np.rint(fov_init_loc).astype(np.int32)  (not clipped)   fov_env.py:149-150
         ctx->init_r = (int)std::nearbyint(c.init_loc[0]);
         ctx->init_c = (int)std::nearbyint(c.init_loc[1]);
-        if (ctx->init_r < 0 || ctx->init_c < 0 || ctx->init_r > c.obs_h - c.fov_h || ctx->init_c > c.obs_w - c.fov_w) {
-            fail(ctx, AGX_E_INVALID, "fov_init_loc (%g,%g) puts the %dx%d window outside the %dx%d frame", c.init_loc[0],
-                 c.init_loc[1], c.fov_h, c.fov_w, c.obs_h, c.obs_w);
-            return bail(AGX_E_INVALID);
-        }
+        if (ctx->init_r < 0 || ctx->init_c < 0 || ctx->init_r > c.obs_h - c.fov_h || ctx->init_c > c.obs_w - c.fov_w)
+            return fail(ctx, AGX_E_INVALID, "fov_init_loc (%g,%g) puts the %dx%d window outside the %dx%d frame", c.init_loc[0],
+                        c.init_loc[1], c.fov_h, c.fov_w, c.obs_h, c.obs_w);
         std::vector<int32_t> loc(2 * N), res(2 * N);
         for (size_t i = 0; i < N; ++i) {
             loc[2 * i] = ctx->init_r;
@@ -595,29 +598,29 @@ int agx_create(const agx_config *cfg, agx_ctx **out) {
             res[2 * i + 1] = c.fov_w;
         }
         for (int b = 0; b < 2; ++b) {
-            if ((rc = upload(ctx, &ctx->loc[b], loc)) != AGX_OK) return bail(rc);
-            if ((rc = upload(ctx, &ctx->res[b], res)) != AGX_OK) return bail(rc);
+            if ((rc = upload(ctx, &ctx->loc[b], loc)) != AGX_OK) return rc;
+            if ((rc = upload(ctx, &ctx->res[b], res)) != AGX_OK) return rc;
         }
         if (c.kind == AGX_KIND_FLEXIBLE) {
             HostFamily fam[6];
             const size_t tab_floats = build_families(c, fam);   // worst-case LDS floats of the staged tables
             for (int k = 0; k < 6; ++k) {
-                if ((rc = upload(ctx, &ctx->flex_ln[k], fam[k].ln)) != AGX_OK) return bail(rc);
-                if ((rc = upload(ctx, &ctx->flex_w[k], fam[k].w)) != AGX_OK) return bail(rc);
-                if ((rc = upload(ctx, &ctx->flex_meta[k], fam[k].meta)) != AGX_OK) return bail(rc);
+                if ((rc = upload(ctx, &ctx->flex_ln[k], fam[k].ln)) != AGX_OK) return rc;
+                if ((rc = upload(ctx, &ctx->flex_w[k], fam[k].w)) != AGX_OK) return rc;
+                if ((rc = upload(ctx, &ctx->flex_meta[k], fam[k].meta)) != AGX_OK) return rc;
             }
             // resize_to_full: the composed-operator kernel where its plan applies (thread-per-column, <= 16 taps)
             const Flex3Host f3 = build_flex3(c);
             if (flex3_fits(f3, c)) {
                 Flex3Params &q = ctx->f3;
-                if ((rc = upload_owned(ctx, &q.wf, f3.wf)) != AGX_OK) return bail(rc);
-                if ((rc = upload_owned(ctx, &q.wc_meta, f3.wc_meta)) != AGX_OK) return bail(rc);
-                if ((rc = upload_owned(ctx, &q.wc_lo, f3.wc_lo)) != AGX_OK) return bail(rc);
-                if ((rc = upload_owned(ctx, &q.wc_w, f3.wc_w)) != AGX_OK) return bail(rc);
-                if ((rc = upload_owned(ctx, &q.hd_meta, f3.hd_meta)) != AGX_OK) return bail(rc);
-                if ((rc = upload_owned(ctx, &q.hd_lo, f3.hd_lo)) != AGX_OK) return bail(rc);
-                if ((rc = upload_owned(ctx, &q.hd_w, f3.hd_w)) != AGX_OK) return bail(rc);
-                if ((rc = upload_owned(ctx, &q.hy, f3.hy)) != AGX_OK) return bail(rc);
+                if ((rc = upload(ctx, &q.wf, f3.wf)) != AGX_OK) return rc;
+                if ((rc = upload(ctx, &q.wc_meta, f3.wc_meta)) != AGX_OK) return rc;
+                if ((rc = upload(ctx, &q.wc_lo, f3.wc_lo)) != AGX_OK) return rc;
+                if ((rc = upload(ctx, &q.wc_w, f3.wc_w)) != AGX_OK) return rc;
+                if ((rc = upload(ctx, &q.hd_meta, f3.hd_meta)) != AGX_OK) return rc;
+                if ((rc = upload(ctx, &q.hd_lo, f3.hd_lo)) != AGX_OK) return rc;
+                if ((rc = upload(ctx, &q.hd_w, f3.hd_w)) != AGX_OK) return rc;
+                if ((rc = upload(ctx, &q.hy, f3.hy)) != AGX_OK) return rc;
                 q.r0_bytes = f3.r0_bytes;
                 q.r1_bytes = f3.r1_bytes;
                 q.dp = f3.dp;
@@ -626,13 +629,13 @@ int agx_create(const agx_config *cfg, agx_ctx **out) {
             const FlexRawHost fr = build_flexraw(c);
             if (flexraw_fits(fr, c)) {
                 FlexRawParams &q = ctx->fr;
-                if ((rc = upload_owned(ctx, &q.wb_meta, fr.wb_meta)) != AGX_OK) return bail(rc);
-                if ((rc = upload_owned(ctx, &q.wb_lo, fr.wb_lo)) != AGX_OK) return bail(rc);
-                if ((rc = upload_owned(ctx, &q.wb_w, fr.wb_w)) != AGX_OK) return bail(rc);
-                if ((rc = upload_owned(ctx, &q.hd_meta, fr.hd_meta)) != AGX_OK) return bail(rc);
-                if ((rc = upload_owned(ctx, &q.hd_lo, fr.hd_lo)) != AGX_OK) return bail(rc);
-                if ((rc = upload_owned(ctx, &q.hd_w, fr.hd_w)) != AGX_OK) return bail(rc);
-                if ((rc = upload_owned(ctx, &q.hb, fr.hb)) != AGX_OK) return bail(rc);
+                if ((rc = upload(ctx, &q.wb_meta, fr.wb_meta)) != AGX_OK) return rc;
+                if ((rc = upload(ctx, &q.wb_lo, fr.wb_lo)) != AGX_OK) return rc;
+                if ((rc = upload(ctx, &q.wb_w, fr.wb_w)) != AGX_OK) return rc;
+                if ((rc = upload(ctx, &q.hd_meta, fr.hd_meta)) != AGX_OK) return rc;
+                if ((rc = upload(ctx, &q.hd_lo, fr.hd_lo)) != AGX_OK) return rc;
+                if ((rc = upload(ctx, &q.hd_w, fr.hd_w)) != AGX_OK) return rc;
+                if ((rc = upload(ctx, &q.hb, fr.hb)) != AGX_OK) return rc;
                 q.r0_bytes = fr.r0_bytes;
                 q.r1_bytes = fr.r1_bytes;
                 q.dp = fr.dp;
@@ -641,10 +644,8 @@ int agx_create(const agx_config *cfg, agx_ctx **out) {
             ctx->plan = plan_flexible(c, tune, f3, fr, tab_floats);
             if (c.out_mode == AGX_OUT_RAW) {       // the packed form's scan buffers
                 const size_t nb = (N + kScanEnvsPerBlock - 1) / kScanEnvsPerBlock;
-                TRY(hipMalloc(reinterpret_cast<void **>(&ctx->pack_local), N * sizeof(int64_t)));
-                ctx->owned.push_back(ctx->pack_local);
-                TRY(hipMalloc(reinterpret_cast<void **>(&ctx->pack_block), nb * sizeof(int64_t)));
-                ctx->owned.push_back(ctx->pack_block);
+                AGX_HIP(ctx, ctx->own.device_mem(&ctx->pack_local, N * sizeof(int64_t)));
+                AGX_HIP(ctx, ctx->own.device_mem(&ctx->pack_block, nb * sizeof(int64_t)));
             }
         }
         if (c.kind == AGX_KIND_PERIPHERAL) {
@@ -656,18 +657,18 @@ int agx_create(const agx_config *cfg, agx_ctx **out) {
                 axis_taps(nin[k], nout[k], c.antialias != 0, ln, w, ctx->per_maxt[k]);
                 if (k == 0)                          // the first pass reads u8 numerators: fold the /255 into its weights
                     for (float &v : w) v = (float)((double)v / 255.0);
-                if ((rc = upload(ctx, &ctx->per_ln[k], ln)) != AGX_OK) return bail(rc);
-                if ((rc = upload(ctx, &ctx->per_w[k], w)) != AGX_OK) return bail(rc);
+                if ((rc = upload(ctx, &ctx->per_ln[k], ln)) != AGX_OK) return rc;
+                if ((rc = upload(ctx, &ctx->per_w[k], w)) != AGX_OK) return rc;
             }
             const Per3Host h3 = build_per3(c);
             if (per3_fits(h3)) {
                 Per3Params &q = ctx->p3;
-                if ((rc = upload_owned(ctx, &q.lo0, h3.lo0)) != AGX_OK) return bail(rc);
-                if ((rc = upload_owned(ctx, &q.w0, h3.w0)) != AGX_OK) return bail(rc);
-                if ((rc = upload_owned(ctx, &q.lo1, h3.lo1)) != AGX_OK) return bail(rc);
-                if ((rc = upload_owned(ctx, &q.w1, h3.w1)) != AGX_OK) return bail(rc);
-                if ((rc = upload_owned(ctx, &q.x2, h3.x2)) != AGX_OK) return bail(rc);
-                if ((rc = upload_owned(ctx, &q.y3, h3.y3)) != AGX_OK) return bail(rc);
+                if ((rc = upload(ctx, &q.lo0, h3.lo0)) != AGX_OK) return rc;
+                if ((rc = upload(ctx, &q.w0, h3.w0)) != AGX_OK) return rc;
+                if ((rc = upload(ctx, &q.lo1, h3.lo1)) != AGX_OK) return rc;
+                if ((rc = upload(ctx, &q.w1, h3.w1)) != AGX_OK) return rc;
+                if ((rc = upload(ctx, &q.x2, h3.x2)) != AGX_OK) return rc;
+                if ((rc = upload(ctx, &q.y3, h3.y3)) != AGX_OK) return rc;
             }
             ctx->plan = plan_peripheral(c, tune, h3, ctx->per_maxt);
             ctx->p3.same = ctx->plan.same;
@@ -677,12 +678,10 @@ int agx_create(const agx_config *cfg, agx_ctx **out) {
             std::vector<Tap> xt(c.obs_w), yt(c.obs_h);
             for (int i = 0; i < c.obs_w; ++i) xt[i] = make_tap_lin2(i, c.fov_w, c.obs_w);
             for (int i = 0; i < c.obs_h; ++i) yt[i] = make_tap_lin2(i, c.fov_h, c.obs_h);
-            if ((rc = upload(ctx, &ctx->fx_xtab, xt)) != AGX_OK) return bail(rc);
-            if ((rc = upload(ctx, &ctx->fx_ytab, yt)) != AGX_OK) return bail(rc);
+            if ((rc = upload(ctx, &ctx->fx_xtab, xt)) != AGX_OK) return rc;
+            if ((rc = upload(ctx, &ctx->fx_ytab, yt)) != AGX_OK) return rc;
         }
     }
-#undef TRY
-    *out = ctx;
     return AGX_OK;
 }
 

@@ -4,15 +4,14 @@
 #include "agx_augment.h"
 
 struct agx_shift {
+    explicit agx_shift(int device) : own(device) {}
+    Resources own;                  // the one device block, below (on the history's device: destroy needs no live history)
     agx_history *h = nullptr;
-    int device = 0;                 // the history's device: destroy needs no live history
     int32_t pad = 0;
-    uint64_t *state = nullptr;      // the one device allocation: u64 [3] seed, calls, the draw launch's ticket counter
+    uint64_t *state = nullptr;      // u64 [3] seed, calls, the draw launch's ticket counter
 };
 
 namespace {
-
-constexpr size_t kShiftStateBytes = 256;
 
 int shift_bad_pad(agx_ctx *ctx, const char *who, int32_t pad) {
     return fail(ctx, AGX_E_INVALID, "%s: pad must be 0 .. %d, got %d", who, AGX_SHIFT_PAD_LIMIT, pad);
@@ -29,29 +28,24 @@ int agx_shift_create(agx_history *h, int32_t pad, agx_shift **out) {
     if (!out) return fail(ctx, AGX_E_INVALID, "agx_shift_create: null out");
     if (!h) return fail(ctx, AGX_E_INVALID, "agx_shift_create: null h");
     if (!full_range(ctx)) return hist_refuse_range(h, "agx_shift_create");
-    agx_shift *s = new (std::nothrow) agx_shift;
+    agx_shift *s = new (std::nothrow) agx_shift(ctx->cfg.device);
     if (!s) return fail(ctx, AGX_E_NOMEM, "out of host memory");
     s->h = h;
-    s->device = ctx->cfg.device;
     s->pad = pad;
-    DeviceGuard g(s->device);
-    hipError_t e = hipMalloc(reinterpret_cast<void **>(&s->state), kShiftStateBytes);
-    if (e == hipSuccess) e = hipMemset(s->state, 0, kShiftStateBytes);          // seed 0, calls 0, no ticket taken
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        if (s->state) (void)hipFree(s->state);
-        delete s;
-        return fail(ctx, e == hipErrorOutOfMemory ? AGX_E_NOMEM : AGX_E_HIP, "agx_shift_create: %zu bytes of device memory: %s", kShiftStateBytes,
-                    hipGetErrorString(e));
-    }
+    agx::BlockLayout lay;
+    const size_t o_state = lay.add(3 * sizeof(uint64_t));
+    DeviceGuard g(s->own.device);
+    uint8_t *block = nullptr;
+    if (int rc = hist_block(ctx, "agx_shift_create", s, lay.bytes(), &block, [&](uint8_t *b) { return hipMemset(b, 0, lay.bytes()); }))      // seed 0, calls 0, no ticket taken
+        return rc;
+    s->state = lay.at<uint64_t>(block, o_state);
     *out = s;
     return AGX_OK;
 }
 
 int agx_shift_destroy(agx_shift *s) {
     if (!s) return AGX_OK;
-    DeviceGuard g(s->device);
-    if (s->state) (void)hipFree(s->state);
+    DeviceGuard g(s->own.device);
     delete s;
     return AGX_OK;
 }
@@ -60,7 +54,7 @@ int agx_shift_seed(agx_shift *s, uint64_t seed, void *stream) {
     if (!s) return fail(nullptr, AGX_E_INVALID, "agx_shift_seed: null s");
     agx_ctx *ctx = s->h->ctx;
     if (!full_range(ctx)) return hist_refuse_range(s->h, "agx_shift_seed");
-    DeviceGuard g(s->device);
+    DeviceGuard g(s->own.device);
     hipLaunchKernelGGL(agx::k_shift_seed, dim3(1), dim3(64), 0, S(stream), s->state, seed);
     AGX_HIP(ctx, hipGetLastError());
     return AGX_OK;
@@ -73,7 +67,7 @@ int agx_shift_draw(agx_shift *s, int32_t B, int32_t *d_shift, void *stream) {
     if (!s) return fail(ctx, AGX_E_INVALID, "agx_shift_draw: null s");
     if (!full_range(ctx)) return hist_refuse_range(s->h, "agx_shift_draw");
     if (B == 0) return AGX_OK;
-    DeviceGuard g(s->device);
+    DeviceGuard g(s->own.device);
     hipLaunchKernelGGL(agx::k_shift_draw, dim3((B + kThreads - 1) / kThreads), dim3(kThreads), 0, S(stream), s->state, s->pad, B, d_shift);
     AGX_HIP(ctx, hipGetLastError());
     return AGX_OK;

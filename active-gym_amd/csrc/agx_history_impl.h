@@ -4,16 +4,28 @@
 #include "agx_history.h"
 
 struct agx_history {
+    explicit agx_history(int device) : own(device) {}
+    Resources own;                  // the one device block: frames | loc | count | age
     agx_ctx *ctx = nullptr;
     int T = 0;
-    uint8_t *block = nullptr;       // the one device allocation: frames | loc | count | age
     size_t bytes = 0;
     agx::HistParams p{};
 };
 
 namespace {
 
-size_t hist_align(size_t b) { return (b + 255) & ~(size_t)255; }
+// The one device block of a handle on the history side (the history itself, replay, step log, priorities, shifts,
+// minibatches): `bytes` from the handle's owner, then fill(block) sets its initial contents.  When either fails the handle is
+// deleted (which gives the block back), the runtime's sticky error is cleared and the message is ctx's.
+template <class H, class Fill>
+int hist_block(agx_ctx *ctx, const char *who, H *handle, size_t bytes, uint8_t **block, Fill &&fill) {
+    hipError_t e = handle->own.device_mem(block, bytes);
+    if (e == hipSuccess) e = fill(*block);
+    if (e == hipSuccess) return AGX_OK;
+    (void)hipGetLastError();
+    delete handle;
+    return fail(ctx, e == hipErrorOutOfMemory ? AGX_E_NOMEM : AGX_E_HIP, "%s: %zu bytes of device memory: %s", who, bytes, hipGetErrorString(e));
+}
 
 int hist_refuse_range(agx_history *h, const char *who) { return refuse_range(h->ctx, who); }
 
@@ -112,49 +124,37 @@ int agx_history_create(agx_ctx *ctx, int32_t capacity, agx_history **out) {
     if (!full_range(ctx)) return refuse_range(ctx, "agx_history_create");
     if (capacity < c.frame_stack)
         return fail(ctx, AGX_E_INVALID, "agx_history_create: capacity %d is below frame_stack %d", capacity, c.frame_stack);
-    agx_history *h = new (std::nothrow) agx_history;
+    agx_history *h = new (std::nothrow) agx_history(c.device);
     if (!h) return fail(ctx, AGX_E_NOMEM, "out of host memory");
     h->ctx = ctx;
     h->T = capacity;
     const size_t T = (size_t)capacity, N = (size_t)c.num_envs, fbytes = (size_t)c.obs_h * c.obs_w;
-    const size_t b_frames = hist_align(T * N * fbytes), b_loc = hist_align(T * N * 2 * sizeof(int32_t)), b_count = hist_align(N * sizeof(int64_t)),
-                 b_age = hist_align(T * N);      // (whole dwords: the scalar byte load reads the aligned dword around a byte)
-    h->bytes = b_frames + b_loc + b_count + b_age;
+    agx::BlockLayout lay;
+    const size_t o_frames = lay.add(T * N * fbytes), o_loc = lay.add(T * N * 2 * sizeof(int32_t)), o_count = lay.add(N * sizeof(int64_t)),
+                 o_age = lay.add(T * N);         // (padded to whole dwords: the scalar byte load reads the aligned dword around a byte)
+    h->bytes = lay.bytes();
     DeviceGuard g(c.device);
-    hipError_t e = hipMalloc(reinterpret_cast<void **>(&h->block), h->bytes);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        const size_t want = h->bytes;
-        delete h;
-        if (e == hipErrorOutOfMemory)
-            return fail(ctx, AGX_E_NOMEM, "agx_history_create: %zu bytes of device memory for %d x %d env-steps: %s", want, capacity, c.num_envs,
-                        hipGetErrorString(e));
-        return fail(ctx, AGX_E_HIP, "agx_history_create: hipMalloc(%zu): %s", want, hipGetErrorString(e));
-    }
+    uint8_t *block = nullptr;
+    if (int rc = hist_block(ctx, "agx_history_create", h, lay.bytes(), &block,          // counts and ages zero; frames and loc as they come
+                            [&](uint8_t *b) { return hipMemset(b + o_count, 0, lay.bytes() - o_count); }))
+        return rc;
     agx::HistParams &p = h->p;
-    p.frames = h->block;
-    p.loc = reinterpret_cast<int32_t *>(h->block + b_frames);
-    p.count = reinterpret_cast<int64_t *>(h->block + b_frames + b_loc);
-    p.age = h->block + b_frames + b_loc + b_count;
+    p.frames = lay.at<uint8_t>(block, o_frames);
+    p.loc = lay.at<int32_t>(block, o_loc);
+    p.count = lay.at<int64_t>(block, o_count);
+    p.age = lay.at<uint8_t>(block, o_age);
     p.T = capacity;
     p.N = c.num_envs;
     p.fs = c.frame_stack;
     p.fbytes = (int32_t)fbytes;
     p.start_age = -1;
-    e = hipMemset(p.count, 0, b_count + b_age);
-    if (e != hipSuccess) {
-        (void)hipFree(h->block);
-        delete h;
-        return fail(ctx, AGX_E_HIP, "agx_history_create: hipMemset: %s", hipGetErrorString(e));
-    }
     *out = h;
     return AGX_OK;
 }
 
 int agx_history_destroy(agx_history *h) {
     if (!h) return AGX_OK;
-    DeviceGuard g(h->ctx->cfg.device);
-    if (h->block) (void)hipFree(h->block);
+    DeviceGuard g(h->own.device);
     delete h;
     return AGX_OK;
 }

@@ -10,6 +10,8 @@
 #include "agx_hostout.h"
 
 struct agx_hostout {
+    explicit agx_hostout(int device) : own(device) {}
+    Resources own;                                    // owns the stream, events and pinned side sets below
     hipStream_t d2h = nullptr;
     hipEvent_t ev_h2d[AGX_HOSTOUT_MAX_CHUNKS] = {};   // copy stream: chunk c's screens are on the device
     hipEvent_t ev_k[AGX_HOSTOUT_MAX_CHUNKS] = {};     // launch stream: chunk c's rows are written
@@ -24,23 +26,7 @@ struct agx_hostout {
     bool has_final = false;                           // the last step filled side set `set`
 };
 
-static void hostout_free(agx_hostout *h) {
-    if (!h) return;
-    if (h->d2h) (void)hipStreamDestroy(h->d2h);
-    for (int c = 0; c < AGX_HOSTOUT_MAX_CHUNKS; ++c) {
-        if (h->ev_h2d[c]) (void)hipEventDestroy(h->ev_h2d[c]);
-        if (h->ev_k[c]) (void)hipEventDestroy(h->ev_k[c]);
-    }
-    if (h->ev_chunks) (void)hipEventDestroy(h->ev_chunks);
-    if (h->ev_tail) (void)hipEventDestroy(h->ev_tail);
-    for (int b = 0; b < 2; ++b) {
-        if (h->ev_done[b]) (void)hipEventDestroy(h->ev_done[b]);
-        if (h->h_final_obs[b]) (void)hipHostFree(h->h_final_obs[b]);
-        if (h->h_final_loc[b]) (void)hipHostFree(h->h_final_loc[b]);
-        if (h->h_final_res[b]) (void)hipHostFree(h->h_final_res[b]);
-    }
-    delete h;
-}
+static void hostout_free(agx_hostout *h) { delete h; }
 
 namespace {
 
@@ -48,22 +34,22 @@ namespace {
 // buffers; no allocation in later steps
 int hostout_alloc(agx_loop *l, agx_hostout *h) {
     const size_t N = (size_t)l->N;
-    LOOP_HIP(l, hipStreamCreateWithFlags(&h->d2h, hipStreamNonBlocking));
-    LOOP_HIP(l, hipEventCreateWithFlags(&h->ev_chunks, hipEventDisableTiming));
-    LOOP_HIP(l, hipEventCreateWithFlags(&h->ev_tail, hipEventDisableTiming));
+    LOOP_HIP(l, h->own.stream(&h->d2h, hipStreamNonBlocking));
+    LOOP_HIP(l, h->own.event(&h->ev_chunks, hipEventDisableTiming));
+    LOOP_HIP(l, h->own.event(&h->ev_tail, hipEventDisableTiming));
     for (int b = 0; b < 2; ++b) {
-        LOOP_HIP(l, hipEventCreateWithFlags(&h->ev_done[b], hipEventDisableTiming));
-        LOOP_HIP(l, hipHostMalloc(&h->h_final_obs[b], N * l->obs_row_bytes, hipHostMallocDefault));
+        LOOP_HIP(l, h->own.event(&h->ev_done[b], hipEventDisableTiming));
+        LOOP_HIP(l, h->own.pinned(&h->h_final_obs[b], N * l->obs_row_bytes));
         if (l->fovea) {
-            LOOP_HIP(l, hipHostMalloc(reinterpret_cast<void **>(&h->h_final_loc[b]), N * 2 * sizeof(int32_t), hipHostMallocDefault));
-            LOOP_HIP(l, hipHostMalloc(reinterpret_cast<void **>(&h->h_final_res[b]), N * 2 * sizeof(int32_t), hipHostMallocDefault));
+            LOOP_HIP(l, h->own.pinned(&h->h_final_loc[b], N * 2 * sizeof(int32_t)));
+            LOOP_HIP(l, h->own.pinned(&h->h_final_res[b], N * 2 * sizeof(int32_t)));
         }
     }
     return AGX_OK;
 }
 int hostout_make(agx_loop *l, int nchunks) {
     if (!l->ho) {
-        agx_hostout *h = new (std::nothrow) agx_hostout;
+        agx_hostout *h = new (std::nothrow) agx_hostout(l->own.device);
         if (!h) return lfail(l, AGX_E_NOMEM, "out of host memory");
         const int rc = hostout_alloc(l, h);
         if (rc != AGX_OK) {                       // all or nothing: a later call starts over
@@ -73,8 +59,8 @@ int hostout_make(agx_loop *l, int nchunks) {
         l->ho = h;
     }
     for (int c = 0; c < nchunks; ++c) {
-        if (!l->ho->ev_h2d[c]) LOOP_HIP(l, hipEventCreateWithFlags(&l->ho->ev_h2d[c], hipEventDisableTiming));
-        if (!l->ho->ev_k[c]) LOOP_HIP(l, hipEventCreateWithFlags(&l->ho->ev_k[c], hipEventDisableTiming));
+        if (!l->ho->ev_h2d[c]) LOOP_HIP(l, l->ho->own.event(&l->ho->ev_h2d[c], hipEventDisableTiming));
+        if (!l->ho->ev_k[c]) LOOP_HIP(l, l->ho->own.event(&l->ho->ev_k[c], hipEventDisableTiming));
     }
     return AGX_OK;
 }

@@ -45,6 +45,8 @@ struct agx_hostout;                   // agx_loop_step_host's streams, events an
 static void hostout_free(agx_hostout *h);
 
 struct agx_loop {
+    explicit agx_loop(int device) : own(device) {}
+    Resources own;                    // owns the pinned sets, device sets, events and the copy stream below
     agx_ctx *ctx = nullptr;
     agx_hostout *ho = nullptr;        // made by the first agx_loop_step_host
     agx_history *hist = nullptr;      // agx_loop_set_history (include/agx_history.h): pushed after every observation
@@ -196,6 +198,36 @@ int loop_reset_subset(agx_loop *l, int k, float *d_obs, int32_t *d_loc, int32_t 
     return AGX_OK;
 }
 
+// What agx_loop_create acquires.  Any failure leaves its message in l->err and returns; agx_loop_create destroys the loop, which
+// gives back whatever was made.
+int loop_build(agx_loop *l) {
+    const size_t N = (size_t)l->N;
+    Resources &r = l->own;
+    // pinned staging: allocated by the calling thread (bind it to the GPU's NUMA node first: first touch - hostplan.bound_to)
+    for (int b = 0; b < 2; ++b) {
+        LOOP_HIP(l, r.pinned(&l->h_frames[b], N * 2 * l->screen_bytes));
+        LOOP_HIP(l, r.pinned(&l->h_cmd[b], N));
+        LOOP_HIP(l, r.pinned(&l->h_rframes[b], N * l->screen_bytes));
+        LOOP_HIP(l, r.pinned(&l->h_rmeta[b], 6 * N));
+        LOOP_HIP(l, r.device_mem(&l->d_frames[b], N * 2 * l->screen_bytes + 2 * l->screen_bytes));   // + slack: K1 loads both screens speculatively
+        LOOP_HIP(l, hipMemset(l->d_frames[b], 0, N * 2 * l->screen_bytes + 2 * l->screen_bytes));
+        LOOP_HIP(l, r.device_mem(&l->d_cmd[b], N));
+        LOOP_HIP(l, r.event(&l->ev_copy[b], hipEventDisableTiming));
+        LOOP_HIP(l, r.event(&l->ev_free[b], hipEventDisableTiming));
+        LOOP_HIP(l, r.event(&l->ev_r[b], hipEventDisableTiming));
+    }
+    LOOP_HIP(l, r.event(&l->ev_rfree, hipEventDisableTiming));
+    LOOP_HIP(l, r.stream(&l->copy_stream, hipStreamNonBlocking));
+    LOOP_HIP(l, r.device_mem(&l->d_rframes, N * l->screen_bytes));
+    LOOP_HIP(l, r.device_mem(&l->d_rmeta, 6 * N));
+    LOOP_HIP(l, r.device_mem(&l->d_final_obs, N * l->obs_row_bytes));
+    if (l->fovea) {
+        LOOP_HIP(l, r.device_mem(&l->d_final_loc, N * 2 * sizeof(int32_t)));
+        LOOP_HIP(l, r.device_mem(&l->d_final_res, N * 2 * sizeof(int32_t)));
+    }
+    return AGX_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -204,25 +236,9 @@ const char *agx_loop_last_error(const agx_loop *loop) { return loop ? loop->err.
 
 int agx_loop_destroy(agx_loop *l) {
     if (!l) return AGX_OK;
-    DeviceGuard g(l->ctx->cfg.device);
+    DeviceGuard g(l->own.device);
     (void)hipDeviceSynchronize();                      // copies from the pinned sets may still be in flight
-    if (l->ho) hostout_free(l->ho);
-    for (int b = 0; b < 2; ++b) {
-        if (l->h_frames[b]) (void)hipHostFree(l->h_frames[b]);
-        if (l->h_cmd[b]) (void)hipHostFree(l->h_cmd[b]);
-        if (l->d_frames[b]) (void)hipFree(l->d_frames[b]);
-        if (l->d_cmd[b]) (void)hipFree(l->d_cmd[b]);
-        if (l->h_rframes[b]) (void)hipHostFree(l->h_rframes[b]);
-        if (l->h_rmeta[b]) (void)hipHostFree(l->h_rmeta[b]);
-        if (l->ev_copy[b]) (void)hipEventDestroy(l->ev_copy[b]);
-        if (l->ev_free[b]) (void)hipEventDestroy(l->ev_free[b]);
-        if (l->ev_r[b]) (void)hipEventDestroy(l->ev_r[b]);
-    }
-    if (l->ev_rfree) (void)hipEventDestroy(l->ev_rfree);
-    if (l->copy_stream) (void)hipStreamDestroy(l->copy_stream);
-    void *dev[] = {l->d_rframes, l->d_rmeta, l->d_final_obs, l->d_final_loc, l->d_final_res};
-    for (void *p : dev)
-        if (p) (void)hipFree(p);
+    hostout_free(l->ho);                               // the host-output side first, then the loop's own resources
     delete l;
     return AGX_OK;
 }
@@ -238,7 +254,7 @@ int agx_loop_create(agx_ctx *ctx, const agx_host_source *src, const agx_loop_con
     const agx_config &c = ctx->cfg;
     // (the flexible raw-crop mode is stepped in its PADDED form here - agx_fovea_flexible into [N][fs][obs_h][obs_w]; a caller who
     //  wants the packed ragged crops runs agx_fovea_flexible_packed itself: active_gym/vector.py keeps that on its Python loop)
-    agx_loop *l = new (std::nothrow) agx_loop;
+    agx_loop *l = new (std::nothrow) agx_loop(c.device);
     if (!l) return lfail(nullptr, AGX_E_NOMEM, "out of host memory");
     l->ctx = ctx;
     l->src = *src;
@@ -259,42 +275,12 @@ int agx_loop_create(agx_ctx *ctx, const agx_host_source *src, const agx_loop_con
     l->done_idx.reserve(N);
     l->noops.assign(N, 0);
     DeviceGuard g(c.device);
-    auto bail = [&](int code) {
+    const int rc = loop_build(l);
+    if (rc != AGX_OK) {
         g_create_err = l->err;
         agx_loop_destroy(l);
-        return code;
-    };
-#define TRYL(expr)                                                                      \
-    do {                                                                                \
-        hipError_t e_ = (expr);                                                         \
-        if (e_ != hipSuccess) {                                                         \
-            lfail(l, AGX_E_HIP, "%s: %s", #expr, hipGetErrorString(e_));               \
-            return bail(AGX_E_HIP);                                                     \
-        }                                                                               \
-    } while (0)
-    // pinned staging: allocated by the calling thread (bind it to the GPU's NUMA node first: first touch - hostplan.bound_to)
-    for (int b = 0; b < 2; ++b) {
-        TRYL(hipHostMalloc(reinterpret_cast<void **>(&l->h_frames[b]), N * 2 * l->screen_bytes, hipHostMallocDefault));
-        TRYL(hipHostMalloc(reinterpret_cast<void **>(&l->h_cmd[b]), N, hipHostMallocDefault));
-        TRYL(hipHostMalloc(reinterpret_cast<void **>(&l->h_rframes[b]), N * l->screen_bytes, hipHostMallocDefault));
-        TRYL(hipHostMalloc(reinterpret_cast<void **>(&l->h_rmeta[b]), 6 * N, hipHostMallocDefault));
-        TRYL(hipMalloc(reinterpret_cast<void **>(&l->d_frames[b]), N * 2 * l->screen_bytes + 2 * l->screen_bytes));   // + slack: K1 loads both screens speculatively
-        TRYL(hipMemset(l->d_frames[b], 0, N * 2 * l->screen_bytes + 2 * l->screen_bytes));
-        TRYL(hipMalloc(reinterpret_cast<void **>(&l->d_cmd[b]), N));
-        TRYL(hipEventCreateWithFlags(&l->ev_copy[b], hipEventDisableTiming));
-        TRYL(hipEventCreateWithFlags(&l->ev_free[b], hipEventDisableTiming));
-        TRYL(hipEventCreateWithFlags(&l->ev_r[b], hipEventDisableTiming));
+        return rc;
     }
-    TRYL(hipEventCreateWithFlags(&l->ev_rfree, hipEventDisableTiming));
-    TRYL(hipStreamCreateWithFlags(&l->copy_stream, hipStreamNonBlocking));
-    TRYL(hipMalloc(reinterpret_cast<void **>(&l->d_rframes), N * l->screen_bytes));
-    TRYL(hipMalloc(reinterpret_cast<void **>(&l->d_rmeta), 6 * N));
-    TRYL(hipMalloc(reinterpret_cast<void **>(&l->d_final_obs), N * l->obs_row_bytes));
-    if (l->fovea) {
-        TRYL(hipMalloc(reinterpret_cast<void **>(&l->d_final_loc), N * 2 * sizeof(int32_t)));
-        TRYL(hipMalloc(reinterpret_cast<void **>(&l->d_final_res), N * 2 * sizeof(int32_t)));
-    }
-#undef TRYL
     *out = l;
     return AGX_OK;
 }

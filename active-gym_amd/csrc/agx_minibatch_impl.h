@@ -9,9 +9,10 @@ static_assert(AGX_MB_LIVE == agx::kMbLive && AGX_MB_BOOT == agx::kMbBoot && AGX_
 static_assert(agx::kMbBootBit == AGX_ROLLOUT_BOOT, "the BOOT bit is the gather's");
 
 struct agx_minibatch {
+    explicit agx_minibatch(int device) : own(device) {}
+    Resources own;                  // the one device block: off i32 [2][N + 1] | cnt i32 [N] | state u64 [2][3] (on the history's device: destroy
+                                    // needs no live history)
     agx_history *h = nullptr;
-    int device = 0;                 // the history's device: destroy needs no live history
-    uint8_t *block = nullptr;       // the one device allocation: off i32 [2][N + 1] | cnt i32 [N] | state u64 [2][3]
     int32_t *off = nullptr, *cnt = nullptr;
     uint64_t *state = nullptr;
 };
@@ -34,41 +35,35 @@ int agx_minibatch_create(agx_history *h, uint64_t seed, agx_minibatch **out) {
     if (out) *out = nullptr;
     if (!h || !out) return fail(ctx, AGX_E_INVALID, "agx_minibatch_create: null argument");
     if (!full_range(ctx)) return hist_refuse_range(h, "agx_minibatch_create");
-    agx_minibatch *mb = new (std::nothrow) agx_minibatch;
+    agx_minibatch *mb = new (std::nothrow) agx_minibatch(ctx->cfg.device);
     if (!mb) return fail(ctx, AGX_E_NOMEM, "out of host memory");
     mb->h = h;
-    mb->device = ctx->cfg.device;
     const size_t N = (size_t)h->p.N;
-    const size_t b_off = hist_align(2 * (N + 1) * sizeof(int32_t)), b_cnt = hist_align(N * sizeof(int32_t)), b_state = hist_align(6 * sizeof(uint64_t));
-    const size_t bytes = b_off + b_cnt + b_state;
+    agx::BlockLayout lay;
+    const size_t o_off = lay.add(2 * (N + 1) * sizeof(int32_t)), o_cnt = lay.add(N * sizeof(int32_t)), o_state = lay.add(6 * sizeof(uint64_t));
     uint64_t state[6];
     for (int which = 0; which < 2; ++which) {
         state[which * 3 + 0] = agx::replay_sm(seed, (uint64_t)which);     // base
         state[which * 3 + 1] = 0;                                         // calls
         state[which * 3 + 2] = 0;                                         // the key in flight: none yet (both totals are 0)
     }
-    DeviceGuard g(mb->device);
-    hipError_t e = hipMalloc(reinterpret_cast<void **>(&mb->block), bytes);
-    if (e == hipSuccess) e = hipMemset(mb->block, 0, bytes);
-    if (e == hipSuccess) e = hipMemcpy(mb->block + b_off + b_cnt, state, sizeof state, hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        if (mb->block) (void)hipFree(mb->block);
-        delete mb;
-        return fail(ctx, e == hipErrorOutOfMemory ? AGX_E_NOMEM : AGX_E_HIP, "agx_minibatch_create: %zu bytes of device memory: %s", bytes,
-                    hipGetErrorString(e));
-    }
-    mb->off = reinterpret_cast<int32_t *>(mb->block);
-    mb->cnt = reinterpret_cast<int32_t *>(mb->block + b_off);
-    mb->state = reinterpret_cast<uint64_t *>(mb->block + b_off + b_cnt);
+    DeviceGuard g(mb->own.device);
+    uint8_t *block = nullptr;
+    if (int rc = hist_block(ctx, "agx_minibatch_create", mb, lay.bytes(), &block, [&](uint8_t *b) {
+            const hipError_t e = hipMemset(b, 0, lay.bytes());
+            return e != hipSuccess ? e : hipMemcpy(b + o_state, state, sizeof state, hipMemcpyHostToDevice);
+        }))
+        return rc;
+    mb->off = lay.at<int32_t>(block, o_off);
+    mb->cnt = lay.at<int32_t>(block, o_cnt);
+    mb->state = lay.at<uint64_t>(block, o_state);
     *out = mb;
     return AGX_OK;
 }
 
 int agx_minibatch_destroy(agx_minibatch *mb) {
     if (!mb) return AGX_OK;
-    DeviceGuard g(mb->device);
-    if (mb->block) (void)hipFree(mb->block);
+    DeviceGuard g(mb->own.device);
     delete mb;
     return AGX_OK;
 }
@@ -81,7 +76,7 @@ int agx_minibatch_select(agx_minibatch *mb, int which, int32_t L, const int32_t 
     if (int rc = mb_bad_list(ctx, who, which, L, N)) return rc;
     if (!d_len || (which == AGX_MB_BOOT && !d_ends)) return fail(ctx, AGX_E_INVALID, "%s: null buffer (%s)", who, !d_len ? "d_len" : "d_ends");
     if (!full_range(ctx)) return hist_refuse_range(mb->h, who);
-    DeviceGuard g(mb->device);
+    DeviceGuard g(mb->own.device);
     int32_t *off = mb->off + (size_t)which * (N + 1);
     if (which == AGX_MB_BOOT)
         hipLaunchKernelGGL(agx::k_mb_count, dim3((N + agx::kMbCountThreads - 1) / agx::kMbCountThreads), dim3(agx::kMbCountThreads), 0, S(stream), d_len,
@@ -107,7 +102,7 @@ int agx_minibatch_take(agx_minibatch *mb, int which, int permute, int32_t L, con
         return fail(ctx, AGX_E_INVALID, "%s: null buffer (%s)", who, !d_len ? "d_len" : !io->d_slot ? "d_slot" : "d_ends");
     if (!full_range(ctx)) return hist_refuse_range(mb->h, who);
     if (S_ == 0) return AGX_OK;
-    DeviceGuard g(mb->device);
+    DeviceGuard g(mb->own.device);
     agx::MbTake q;
     q.off = mb->off + (size_t)which * (N + 1);
     q.state = mb->state + which * 3;
@@ -151,7 +146,7 @@ int agx_minibatch_scatter(agx_minibatch *mb, int32_t S_, const int32_t *d_slot, 
         return fail(ctx, AGX_E_INVALID, "%s: null buffer (%s)", who, !d_slot ? "d_slot" : !d_valid ? "d_valid" : !d_src ? "d_src" : "d_dst");
     if (!full_range(ctx)) return hist_refuse_range(mb->h, who);
     if (S_ == 0) return AGX_OK;
-    DeviceGuard g(mb->device);
+    DeviceGuard g(mb->own.device);
     hipLaunchKernelGGL(agx::k_mb_scatter, dim3((uint32_t)(((int64_t)S_ + kThreads - 1) / kThreads)), dim3(kThreads), 0, S(stream), S_, d_slot, d_valid, d_src,
                        L * N, d_dst);
     AGX_HIP(ctx, hipGetLastError());

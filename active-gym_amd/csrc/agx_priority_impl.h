@@ -6,10 +6,11 @@
 static_assert(agx::kPrioChunk + 2 * AGX_REPLAY_SPAN_LIMIT <= agx::kPrioRow, "the age tile of k_priority_weights holds a chunk and both spans");
 
 struct agx_priority {
+    explicit agx_priority(int device) : own(device) {}
+    Resources own;                  // the one device block: stamp | incl | csum | envsum | envacc | off | state | weight | cacc | wmax
+                                    // (on the history's device: destroy needs no live history)
     agx_history *h = nullptr;
-    int device = 0;                 // the history's device: destroy needs no live history
     int32_t back = 0, forward = 0, CH = 0;
-    uint8_t *block = nullptr;       // the one device allocation: stamp | incl | csum | envsum | envacc | off | state | weight | cacc | wmax
     size_t bytes = 0;
     int64_t rows = 0;               // T * N
     int64_t *stamp = nullptr, *incl = nullptr, *csum = nullptr, *envsum = nullptr, *envacc = nullptr, *off = nullptr;
@@ -69,58 +70,46 @@ int agx_priority_create(agx_history *h, int32_t back, int32_t forward, agx_prior
         return fail(ctx, AGX_E_INVALID, "agx_priority_create: T * N must be below 2^31 rows (the i64 sums of u32 weights), got %lld x %lld",
                     (long long)T, (long long)N);
     if (!full_range(ctx)) return hist_refuse_range(h, "agx_priority_create");
-    agx_priority *t = new (std::nothrow) agx_priority;
+    agx_priority *t = new (std::nothrow) agx_priority(ctx->cfg.device);
     if (!t) return fail(ctx, AGX_E_NOMEM, "out of host memory");
     t->h = h;
-    t->device = ctx->cfg.device;
     t->back = back;
     t->forward = forward;
     t->rows = T * N;
     t->CH = (int32_t)((T + agx::kPrioChunk - 1) / agx::kPrioChunk);
     const size_t rows = (size_t)t->rows, chunks = (size_t)N * t->CH;
-    const size_t b_stamp = hist_align(rows * sizeof(int64_t)), b_incl = b_stamp, b_csum = hist_align(chunks * sizeof(int64_t)),
-                 b_env = hist_align((size_t)N * sizeof(int64_t)), b_off = hist_align(((size_t)N + 1) * sizeof(int64_t)),
-                 b_state = hist_align(3 * sizeof(uint64_t)), b_weight = hist_align(rows * sizeof(uint32_t)),
-                 b_cacc = hist_align(chunks * sizeof(int32_t)), b_wmax = hist_align(sizeof(uint32_t));
-    t->bytes = b_stamp + b_incl + b_csum + 2 * b_env + b_off + b_state + b_weight + b_cacc + b_wmax;
+    agx::BlockLayout lay;
+    const size_t o_stamp = lay.add(rows * sizeof(int64_t)), o_incl = lay.add(rows * sizeof(int64_t)), o_csum = lay.add(chunks * sizeof(int64_t)),
+                 o_envsum = lay.add((size_t)N * sizeof(int64_t)), o_envacc = lay.add((size_t)N * sizeof(int64_t)),
+                 o_off = lay.add(((size_t)N + 1) * sizeof(int64_t)), o_state = lay.add(3 * sizeof(uint64_t)),
+                 o_weight = lay.add(rows * sizeof(uint32_t)), o_cacc = lay.add(chunks * sizeof(int32_t)), o_wmax = lay.add(sizeof(uint32_t));
+    t->bytes = lay.bytes();
     const uint32_t one = agx::kPriorityOne;
-    DeviceGuard g(t->device);
-    hipError_t e = hipMalloc(reinterpret_cast<void **>(&t->block), t->bytes);
-    if (e == hipSuccess) e = hipMemset(t->block, 0xFF, b_stamp);                            // every row unset
-    if (e == hipSuccess) e = hipMemset(t->block + b_stamp, 0, t->bytes - b_stamp);          // seed 0, calls 0
-    if (e == hipSuccess) e = hipMemcpy(t->block + t->bytes - b_wmax, &one, sizeof(one), hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        const size_t want = t->bytes;
-        if (t->block) (void)hipFree(t->block);
-        delete t;
-        return fail(ctx, e == hipErrorOutOfMemory ? AGX_E_NOMEM : AGX_E_HIP, "agx_priority_create: %zu bytes of device memory: %s", want,
-                    hipGetErrorString(e));
-    }
-    uint8_t *at = t->block;
-    const auto take = [&at](size_t b) {
-        uint8_t *here = at;
-        at += b;
-        return here;
-    };
-    t->stamp = reinterpret_cast<int64_t *>(take(b_stamp));
-    t->incl = reinterpret_cast<int64_t *>(take(b_incl));
-    t->csum = reinterpret_cast<int64_t *>(take(b_csum));
-    t->envsum = reinterpret_cast<int64_t *>(take(b_env));
-    t->envacc = reinterpret_cast<int64_t *>(take(b_env));
-    t->off = reinterpret_cast<int64_t *>(take(b_off));
-    t->state = reinterpret_cast<uint64_t *>(take(b_state));
-    t->weight = reinterpret_cast<uint32_t *>(take(b_weight));
-    t->cacc = reinterpret_cast<int32_t *>(take(b_cacc));
-    t->wmax = reinterpret_cast<uint32_t *>(take(b_wmax));
+    DeviceGuard g(t->own.device);
+    uint8_t *block = nullptr;
+    if (int rc = hist_block(ctx, "agx_priority_create", t, lay.bytes(), &block, [&](uint8_t *b) {
+            hipError_t e = hipMemset(b, 0xFF, o_incl);                                      // the stamp section: every row unset
+            if (e == hipSuccess) e = hipMemset(b + o_incl, 0, lay.bytes() - o_incl);        // seed 0, calls 0
+            return e != hipSuccess ? e : hipMemcpy(b + o_wmax, &one, sizeof(one), hipMemcpyHostToDevice);
+        }))
+        return rc;
+    t->stamp = lay.at<int64_t>(block, o_stamp);
+    t->incl = lay.at<int64_t>(block, o_incl);
+    t->csum = lay.at<int64_t>(block, o_csum);
+    t->envsum = lay.at<int64_t>(block, o_envsum);
+    t->envacc = lay.at<int64_t>(block, o_envacc);
+    t->off = lay.at<int64_t>(block, o_off);
+    t->state = lay.at<uint64_t>(block, o_state);
+    t->weight = lay.at<uint32_t>(block, o_weight);
+    t->cacc = lay.at<int32_t>(block, o_cacc);
+    t->wmax = lay.at<uint32_t>(block, o_wmax);
     *out = t;
     return AGX_OK;
 }
 
 int agx_priority_destroy(agx_priority *t) {
     if (!t) return AGX_OK;
-    DeviceGuard g(t->device);
-    if (t->block) (void)hipFree(t->block);
+    DeviceGuard g(t->own.device);
     delete t;
     return AGX_OK;
 }
@@ -131,7 +120,7 @@ int agx_priority_seed(agx_priority *t, uint64_t seed, void *stream) {
     if (!t) return fail(nullptr, AGX_E_INVALID, "agx_priority_seed: null argument (p)");
     agx_ctx *ctx = t->h->ctx;
     if (!full_range(ctx)) return hist_refuse_range(t->h, "agx_priority_seed");
-    DeviceGuard g(t->device);
+    DeviceGuard g(t->own.device);
     hipLaunchKernelGGL(agx::k_priority_seed, dim3(1), dim3(64), 0, S(stream), t->state, seed);
     AGX_HIP(ctx, hipGetLastError());
     return AGX_OK;
@@ -141,7 +130,7 @@ int agx_priority_clear(agx_priority *t, void *stream) {
     if (!t) return fail(nullptr, AGX_E_INVALID, "agx_priority_clear: null argument (p)");
     agx_ctx *ctx = t->h->ctx;
     if (!full_range(ctx)) return hist_refuse_range(t->h, "agx_priority_clear");
-    DeviceGuard g(t->device);
+    DeviceGuard g(t->own.device);
     hipLaunchKernelGGL(agx::k_priority_clear, dim3(priority_blocks(t->rows, kThreads)), dim3(kThreads), 0, S(stream), t->stamp, t->wmax, t->rows);
     AGX_HIP(ctx, hipGetLastError());
     return AGX_OK;
@@ -150,7 +139,7 @@ int agx_priority_clear(agx_priority *t, void *stream) {
 int agx_priority_update(agx_priority *t, const int32_t *d_env, const int64_t *d_index, const float *d_priority, int32_t B, void *stream) {
     const int rc = priority_pairs(t, "agx_priority_update", d_env, d_index, d_priority, "d_priority", B);
     if (rc != 1) return rc;
-    DeviceGuard g(t->device);
+    DeviceGuard g(t->own.device);
     hipLaunchKernelGGL(agx::k_priority_update, dim3(priority_blocks(B, kThreads)), dim3(kThreads), 0, S(stream), priority_params(t), d_env, d_index,
                        d_priority, B);
     AGX_HIP(t->h->ctx, hipGetLastError());
@@ -160,7 +149,7 @@ int agx_priority_update(agx_priority *t, const int32_t *d_env, const int64_t *d_
 int agx_priority_lookup(agx_priority *t, const int32_t *d_env, const int64_t *d_index, int32_t B, int64_t *d_weight, void *stream) {
     const int rc = priority_pairs(t, "agx_priority_lookup", d_env, d_index, d_weight, "d_weight", B);
     if (rc != 1) return rc;
-    DeviceGuard g(t->device);
+    DeviceGuard g(t->own.device);
     hipLaunchKernelGGL(agx::k_priority_lookup, dim3(priority_blocks(B, kThreads)), dim3(kThreads), 0, S(stream), priority_params(t), d_env, d_index,
                        B, d_weight);
     AGX_HIP(t->h->ctx, hipGetLastError());
@@ -175,7 +164,7 @@ int agx_priority_sample(agx_priority *t, int32_t B, int32_t *d_env, int64_t *d_i
     if (B > 0 && (!d_env || !d_index)) return fail(ctx, AGX_E_INVALID, "agx_priority_sample: null buffer (%s)", !d_env ? "d_env" : "d_index");
     if (!full_range(ctx)) return hist_refuse_range(t->h, "agx_priority_sample");
     if (B == 0) return AGX_OK;
-    DeviceGuard g(t->device);
+    DeviceGuard g(t->own.device);
     const agx::PriorityParams p = priority_params(t);
     const int64_t groups = ((int64_t)p.h.N + agx::kPrioGroup - 1) / agx::kPrioGroup;      // groups * CH < 2^31 / 1024 + N + CH
     hipLaunchKernelGGL(agx::k_priority_weights, dim3((uint32_t)(groups * p.CH)), dim3(kThreads), 0, S(stream), p);

@@ -4,10 +4,10 @@
 #include "agx_replay.h"
 
 struct agx_replay {
+    explicit agx_replay(int device) : own(device) {}
+    Resources own;                  // the one device block: off i64 [N + 1] | state u64 [3] (on the history's device: destroy needs no live history)
     agx_history *h = nullptr;
-    int device = 0;                 // the history's device: destroy needs no live history
     int32_t back = 0, forward = 0, attempts = 0;
-    uint8_t *block = nullptr;       // the one device allocation: off i64 [N + 1] | state u64 [3]
     int64_t *off = nullptr;
     uint64_t *state = nullptr;
 };
@@ -39,34 +39,27 @@ int agx_replay_create(agx_history *h, int32_t back, int32_t forward, int32_t att
         return fail(ctx, AGX_E_INVALID, "agx_replay_create: attempts must be 1 .. %d (0: 16), got %d", AGX_REPLAY_ATTEMPT_LIMIT, attempts);
     if (!h || !out) return fail(ctx, AGX_E_INVALID, "agx_replay_create: null argument");
     if (!full_range(ctx)) return hist_refuse_range(h, "agx_replay_create");
-    agx_replay *r = new (std::nothrow) agx_replay;
+    agx_replay *r = new (std::nothrow) agx_replay(ctx->cfg.device);
     if (!r) return fail(ctx, AGX_E_NOMEM, "out of host memory");
     r->h = h;
-    r->device = ctx->cfg.device;
     r->back = back;
     r->forward = forward;
     r->attempts = attempts == 0 ? 16 : attempts;
-    const size_t b_off = hist_align(((size_t)h->p.N + 1) * sizeof(int64_t)), b_state = hist_align(3 * sizeof(uint64_t));
-    DeviceGuard g(r->device);
-    hipError_t e = hipMalloc(reinterpret_cast<void **>(&r->block), b_off + b_state);
-    if (e == hipSuccess) e = hipMemset(r->block, 0, b_off + b_state);          // seed 0, calls 0
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        if (r->block) (void)hipFree(r->block);
-        delete r;
-        return fail(ctx, e == hipErrorOutOfMemory ? AGX_E_NOMEM : AGX_E_HIP, "agx_replay_create: %zu bytes of device memory: %s", b_off + b_state,
-                    hipGetErrorString(e));
-    }
-    r->off = reinterpret_cast<int64_t *>(r->block);
-    r->state = reinterpret_cast<uint64_t *>(r->block + b_off);
+    agx::BlockLayout lay;
+    const size_t o_off = lay.add(((size_t)h->p.N + 1) * sizeof(int64_t)), o_state = lay.add(3 * sizeof(uint64_t));
+    DeviceGuard g(r->own.device);
+    uint8_t *block = nullptr;
+    if (int rc = hist_block(ctx, "agx_replay_create", r, lay.bytes(), &block, [&](uint8_t *b) { return hipMemset(b, 0, lay.bytes()); }))      // seed 0, calls 0
+        return rc;
+    r->off = lay.at<int64_t>(block, o_off);
+    r->state = lay.at<uint64_t>(block, o_state);
     *out = r;
     return AGX_OK;
 }
 
 int agx_replay_destroy(agx_replay *r) {
     if (!r) return AGX_OK;
-    DeviceGuard g(r->device);
-    if (r->block) (void)hipFree(r->block);
+    DeviceGuard g(r->own.device);
     delete r;
     return AGX_OK;
 }
@@ -75,7 +68,7 @@ int agx_replay_seed(agx_replay *r, uint64_t seed, void *stream) {
     if (!r) return AGX_E_INVALID;
     agx_ctx *ctx = r->h->ctx;
     if (!full_range(ctx)) return hist_refuse_range(r->h, "agx_replay_seed");
-    DeviceGuard g(r->device);
+    DeviceGuard g(r->own.device);
     hipLaunchKernelGGL(agx::k_replay_seed, dim3(1), dim3(64), 0, S(stream), r->state, seed);
     AGX_HIP(ctx, hipGetLastError());
     return AGX_OK;
@@ -88,7 +81,7 @@ int agx_replay_sample(agx_replay *r, int32_t B, int32_t *d_env, int64_t *d_index
     if (B > 0 && (!d_env || !d_index)) return fail(ctx, AGX_E_INVALID, "agx_replay_sample: null buffer");
     if (!full_range(ctx)) return hist_refuse_range(r->h, "agx_replay_sample");
     if (B == 0) return AGX_OK;
-    DeviceGuard g(r->device);
+    DeviceGuard g(r->own.device);
     const agx::ReplayParams p = replay_params(r);
     hipLaunchKernelGGL(agx::k_replay_scan, dim3(1), dim3(kThreads), 0, S(stream), p, d_total);
     hipLaunchKernelGGL(agx::k_replay_draw, dim3((B + kThreads - 1) / kThreads), dim3(kThreads), 0, S(stream), p, B, d_env, d_index, d_ok);

@@ -40,7 +40,7 @@ int agx_rollout_gather(agx_steplog *log, int32_t L, int32_t *d_len, int64_t *d_o
     if (int rc = rollout_bad_L(ctx, who, L, N)) return rc;
     if (!d_obs_index) return fail(ctx, AGX_E_INVALID, "%s: null buffer (d_obs_index)", who);
     if (!full_range(ctx)) return hist_refuse_range(log->h, who);
-    DeviceGuard g(log->device);
+    DeviceGuard g(log->own.device);
     agx::RolloutOut o;
     o.len = d_len;
     o.obs_index = d_obs_index;

@@ -63,7 +63,7 @@ int agx_sequence_gather(agx_steplog *log, const int32_t *d_env, const int64_t *d
     if (!log) return fail(ctx, AGX_E_INVALID, "%s: null argument (log)", who);
     if (B == 0) return AGX_OK;
     if (!full_range(ctx)) return hist_refuse_range(log->h, who);
-    DeviceGuard g(log->device);
+    DeviceGuard g(log->own.device);
     agx::StepLogOut o;
     o.ret = d_ret;
     o.discount = d_discount;

@@ -6,10 +6,10 @@
 static_assert(AGX_STEP_TERMINATED == agx::kStepTerminated && AGX_STEP_TRUNCATED == agx::kStepTruncated, "agx_steplog_fold.h's flag bits are the header's");
 
 struct agx_steplog {
+    explicit agx_steplog(int device) : own(device) {}
+    Resources own;                  // the one device block: stamp | reward | flags | payload (on the history's device: destroy needs no live history)
     agx_history *h = nullptr;
-    int device = 0;                 // the history's device: destroy needs no live history
     int32_t W = 0;
-    uint8_t *block = nullptr;       // the one device allocation: stamp | reward | flags | payload
     size_t bytes = 0, stamp_bytes = 0;
     float *reward = nullptr;
     uint8_t *flags = nullptr;
@@ -42,47 +42,41 @@ int agx_steplog_create(agx_history *h, int32_t payload_bytes, agx_steplog **out)
                     payload_bytes);
     if (!h || !out) return fail(ctx, AGX_E_INVALID, "agx_steplog_create: null argument (%s)", !h ? "h" : "out");
     if (!full_range(ctx)) return hist_refuse_range(h, "agx_steplog_create");
-    agx_steplog *s = new (std::nothrow) agx_steplog;
+    agx_steplog *s = new (std::nothrow) agx_steplog(ctx->cfg.device);
     if (!s) return fail(ctx, AGX_E_NOMEM, "out of host memory");
     s->h = h;
-    s->device = ctx->cfg.device;
     s->W = payload_bytes;
     const size_t rows = (size_t)h->p.T * h->p.N;
-    const size_t b_stamp = hist_align(rows * sizeof(int64_t)), b_reward = hist_align(rows * sizeof(float)), b_flags = hist_align(rows),
-                 b_payload = hist_align(rows * (size_t)payload_bytes);
-    s->bytes = b_stamp + b_reward + b_flags + b_payload;
+    agx::BlockLayout lay;
+    const size_t o_stamp = lay.add(rows * sizeof(int64_t)), o_reward = lay.add(rows * sizeof(float)), o_flags = lay.add(rows),
+                 o_payload = lay.add(rows * (size_t)payload_bytes);
+    s->bytes = lay.bytes();
     s->stamp_bytes = rows * sizeof(int64_t);
-    DeviceGuard g(s->device);
-    hipError_t e = hipMalloc(reinterpret_cast<void **>(&s->block), s->bytes);
-    if (e == hipSuccess) e = hipMemset(s->block, 0xFF, b_stamp);                            // every row unrecorded
-    if (e == hipSuccess) e = hipMemset(s->block + b_stamp, 0, s->bytes - b_stamp);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        const size_t want = s->bytes;
-        if (s->block) (void)hipFree(s->block);
-        delete s;
-        return fail(ctx, e == hipErrorOutOfMemory ? AGX_E_NOMEM : AGX_E_HIP, "agx_steplog_create: %zu bytes of device memory: %s", want,
-                    hipGetErrorString(e));
-    }
-    s->stamp = reinterpret_cast<int64_t *>(s->block);
-    s->reward = reinterpret_cast<float *>(s->block + b_stamp);
-    s->flags = s->block + b_stamp + b_reward;
-    s->payload = s->block + b_stamp + b_reward + b_flags;
+    DeviceGuard g(s->own.device);
+    uint8_t *block = nullptr;
+    if (int rc = hist_block(ctx, "agx_steplog_create", s, lay.bytes(), &block, [&](uint8_t *b) {
+            const hipError_t e = hipMemset(b, 0xFF, o_reward);                              // the stamp section: every row unrecorded
+            return e != hipSuccess ? e : hipMemset(b + o_reward, 0, lay.bytes() - o_reward);
+        }))
+        return rc;
+    s->stamp = lay.at<int64_t>(block, o_stamp);
+    s->reward = lay.at<float>(block, o_reward);
+    s->flags = lay.at<uint8_t>(block, o_flags);
+    s->payload = lay.at<uint8_t>(block, o_payload);
     *out = s;
     return AGX_OK;
 }
 
 int agx_steplog_destroy(agx_steplog *s) {
     if (!s) return AGX_OK;
-    DeviceGuard g(s->device);
-    if (s->block) (void)hipFree(s->block);
+    DeviceGuard g(s->own.device);
     delete s;
     return AGX_OK;
 }
 
 int agx_steplog_clear(agx_steplog *s, void *stream) {
     if (!s) return fail(nullptr, AGX_E_INVALID, "agx_steplog_clear: null argument (s)");
-    DeviceGuard g(s->device);
+    DeviceGuard g(s->own.device);
     AGX_HIP(s->h->ctx, hipMemsetAsync(s->stamp, 0xFF, s->stamp_bytes, S(stream)));
     return AGX_OK;
 }
@@ -97,7 +91,7 @@ int agx_steplog_record(agx_steplog *s, const int64_t *d_index, const float *d_re
         return fail(ctx, AGX_E_INVALID, "agx_steplog_record: null buffer (%s)", !d_index ? "d_index" : !d_reward ? "d_reward" : "d_flags");
     if (s->W > 0 && !d_payload) return fail(ctx, AGX_E_INVALID, "agx_steplog_record: null buffer (d_payload) on a log with %d payload bytes", s->W);
     if (!full_range(ctx)) return hist_refuse_range(s->h, "agx_steplog_record");
-    DeviceGuard g(s->device);
+    DeviceGuard g(s->own.device);
     const int N = s->h->p.N;
     const uint32_t blocks = (uint32_t)(((int64_t)N + kThreads - 1) / kThreads);
     hipLaunchKernelGGL(agx::k_steplog_record, dim3(blocks), dim3(kThreads), 0, S(stream), steplog_params(s), d_index, d_reward,
@@ -117,7 +111,7 @@ int agx_steplog_gather(agx_steplog *s, const int32_t *d_env, const int64_t *d_in
         return fail(ctx, AGX_E_INVALID, "agx_steplog_gather: null buffer (%s)", !d_env ? "d_env" : !d_index ? "d_index" : "d_steps");
     if (!full_range(ctx)) return hist_refuse_range(s->h, "agx_steplog_gather");
     if (B == 0) return AGX_OK;
-    DeviceGuard g(s->device);
+    DeviceGuard g(s->own.device);
     agx::StepLogOut o;
     o.ret = d_return;
     o.discount = d_discount;

@@ -104,10 +104,10 @@ int exp_step_split(agx_ctx *ctx, int parts, const uint8_t *d_frames, const uint8
         AGX_HIP(ctx, hipDeviceGetStreamPriorityRange(&lo_p, &hi_p));        // lo_p: least urgent (largest number)
         const int prio = tn.aux_prio > 0 ? hi_p : (tn.aux_prio < 0 ? lo_p : 0);
         for (int k = 0; k < 3; ++k) {
-            AGX_HIP(ctx, hipStreamCreateWithPriority(&ctx->aux[k], hipStreamNonBlocking, prio));
-            AGX_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_join[k], hipEventDisableTiming));
+            AGX_HIP(ctx, ctx->own.stream(&ctx->aux[k], hipStreamNonBlocking, prio));
+            AGX_HIP(ctx, ctx->own.event(&ctx->ev_join[k], hipEventDisableTiming));
         }
-        AGX_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_fork, hipEventDisableTiming));
+        AGX_HIP(ctx, ctx->own.event(&ctx->ev_fork, hipEventDisableTiming));
     }
     hipStream_t st[4] = {S(stream), ctx->aux[0], ctx->aux[1], ctx->aux[2]};
     AGX_HIP(ctx, hipEventRecord(ctx->ev_fork, st[0]));

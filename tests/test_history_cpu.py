@@ -68,6 +68,7 @@ def test_source_hash_covers_the_new_files():
     assert os.path.join("include", "agx_history.h") in deps
     assert os.path.join("active-gym_amd", "csrc", "agx_history_impl.h") in deps
     assert os.path.join("active-gym_amd", "csrc", "agx_k5_history.h") in deps
+    assert os.path.join("active-gym_amd", "csrc", "agx_resources.h") in deps      # where the history (and every handle) gets its storage
 
 
 def test_null_arguments_are_invalid_before_any_hip_call():
