@@ -41,6 +41,7 @@ from .rollout import Rollout  # noqa: F401
 from .vtrace import VTrace, BehaviourLog  # noqa: F401
 from .minibatch import Minibatcher  # noqa: F401
 from .retrace import Retrace, coefficients  # noqa: F401
+from .chunks import Chunker  # noqa: F401
 from .sharding import shard_bounds, shard_game, ShardedAtariVecEnv, make_vec_env  # noqa: F401
 
 __version__ = "0.1.0"

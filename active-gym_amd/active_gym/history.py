@@ -196,6 +196,14 @@ class FrameHistory(Owner):
             mb = self._samplers[key] = rollout.minibatcher(seed)
         return mb
 
+    def chunker(self, rollout, seed: int = 0):
+        """The one chunks.Chunker of this seed on this history, made at first use (``rollout``: the Rollout it is made on)."""
+        key = ("chunks", int(seed))
+        ch = self._samplers.get(key)
+        if ch is None:
+            ch = self._samplers[key] = rollout.chunker(seed)
+        return ch
+
     def transition_obs(self, read, env, index, next_index, shift=None) -> dict:
         """The observation part of a transition batch through ``read`` (``self.observe`` or a GlimpseMemory's): obs, next_obs
         and, on a fixed pipeline, fov_loc, next_fov_loc.  ``shift``: the augment.RandomShift whose ``observe`` ``read`` is - two

@@ -1,10 +1,10 @@
-"""Owner — the one place that keeps a raw C handle alive and destroys it: for the nine classes that hold one (ObsPipeline,
-NativeHostRunner, NativeStepLoop, FrameHistory, ReplaySampler, StepLog, PrioritizedSampler, RandomShift, Minibatcher).
+"""Owner — the one place that keeps a raw C handle alive and destroys it: for the ten classes that hold one (ObsPipeline,
+NativeHostRunner, NativeStepLoop, FrameHistory, ReplaySampler, StepLog, PrioritizedSampler, RandomShift, Minibatcher, Chunker).
 
 An object that was built from the raw handles of others names them as its parents and must be gone before any of them is.  The
 tree is
 
-    pipeline -> {history, loop}      runner -> {loop}      history -> {samplers, step logs, shift sources, minibatchers}
+    pipeline -> {history, loop}      runner -> {loop}      history -> {samplers, step logs, shift sources, minibatchers, chunkers}
 
 and ``close()`` of any node closes its children first (in the order they were made), then destroys its own handle, then takes
 itself off its parents' lists; it does so once, however often and from wherever it is called - by the user, by a parent, or by

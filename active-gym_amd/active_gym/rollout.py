@@ -128,6 +128,12 @@ class Rollout:
         from .minibatch import Minibatcher
         return Minibatcher(self, seed)
 
+    def chunker(self, seed: int = 0):
+        """A chunks.Chunker on this rollout's history: the device-side list of a batch's chunks of consecutive steps and its
+        seeded shuffles, for a recurrent learner."""
+        from .chunks import Chunker
+        return Chunker(self, seed)
+
     def flat(self, batch: dict, which: str = "obs"):
         """(env i32 [M], index i64 [M]) of the M live slots, in [L, N] order: the samples of ``FrameHistory.observe`` for the
         observations the actions were taken on (``which = "obs"``) or the ones the steps returned (``"next"``).  A minibatch of

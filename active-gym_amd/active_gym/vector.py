@@ -598,6 +598,54 @@ class AtariVecEnv:
         for first in range(0, cells, size):
             yield self._split_payload(mb.take(batch, first, size, "live", True, streams))
 
+    def rollout_chunks(self, batch: dict, C: int, size: int, streams=None, seed: Optional[int] = None):
+        """One epoch over the chunks of a ``rollout_batch`` - runs of ``C`` consecutive steps of one env that hold a live slot -
+        freshly shuffled on the device, for a RECURRENT on-policy learner: a generator of ``ceil(N * ceil(L / C) / size)`` dicts
+        of ``size`` chunks each (the number is that of a full rollout, so it is no data).  Per step, time-major ``[C, size]``:
+        ``slot``, ``env``, ``obs_index``, ``next_index``, ``ends``, ``start``, ``mask``, ``motor_action`` (i32) and, on a fixed env,
+        ``sensory_action`` (f32 [C, size, 2]), and one f32 entry per name in ``streams`` (a dict name -> f32 [L, N] such as adv /
+        ret / value / logp, or names of entries of ``batch``).  Per chunk, ``[size]``: ``chunk``, ``first``, ``steps``,
+        ``state_index``, ``valid``.  Every live slot is in exactly one step with ``mask = 1``; chunks past the list wrap to real
+        ones with ``mask = 0``, padding steps hold -1 / zeros.  Nothing synchronises.  The whole recipe::
+
+            blog = env.behaviour_log(width=H)
+            ...                                                        # at every act: the state the actor entered the step with
+            blog.write(info["history_index"], h)                       # 1. store the actor's hidden state
+            batch = env.rollout_batch(L)
+            for rows in env.rollout_chunks(batch, C, size, {"adv": adv, "ret": ret}):
+                stored = blog.read(rows["state_index"], rows["env"][0])     # 2. read it back at (env[0], state_index)
+                obs = env.history.observe(rows["env"].flatten(), rows["obs_index"].flatten())[0]    # 3. index -1 is left untouched
+                h = stored
+                for l in range(C):                                     # 4. the RNN over l
+                    h = torch.where((rows["start"][l] & 1).bool()[:, None], stored, h)  #    load the stored state where start & 1 ...
+                    h = torch.where((rows["start"][l] & 2).bool()[:, None], h0, h)      #    ... restart where start & 2
+                    out, h = rnn(obs.view(C, size, *obs.shape[1:])[l], h)
+                loss = (per_step_loss * rows["mask"]).sum() / rows["mask"].sum().clamp(min=1)        # 5. multiply by mask
+
+        Needs ``step_log``: ValueError otherwise."""
+        from .chunks import check_chunk_length, check_rows, check_streams
+        from .minibatch import check_epoch_size
+        roll = self._rollout("rollout_chunks")
+        seed = int(getattr(self.args, "seed", 0) or 0) if seed is None else int(seed)
+        ch = self.history.chunker(roll, seed)
+        L = int(batch["ends"].shape[0])
+        C = check_chunk_length(C, L)
+        size = check_epoch_size(size)
+        check_rows(C, size)
+        streams = check_streams(streams, batch)
+        return self._chunk_epoch(ch, self._with_payload(batch), C, size, streams)
+
+    def _chunk_epoch(self, ch, batch, C, size, streams):
+        cells = self.num_envs * (-(-int(batch["ends"].shape[0]) // C))
+        ch.select(batch, C)
+        for first in range(0, cells, size):
+            rows = ch.take(batch, first, size, C, True, streams)
+            words = rows.pop("payload").view(torch.int32)
+            rows["motor_action"] = words[..., 0].contiguous()
+            if self.kind == "fixed":
+                rows["sensory_action"] = words[..., 1:3].contiguous().view(torch.float32)
+            yield rows
+
     def behaviour_log(self, width: int = 1):
         """A vtrace.BehaviourLog on the env's frame history, cached per width: ``write(info["history_index"], logp)`` at every
         act, ``read(batch["obs_index"])`` after ``rollout_batch``.  Needs ``history_len`` > 0: ValueError otherwise."""

@@ -21,7 +21,8 @@ DEPS = [SRC] + sorted(os.path.join(HERE, "csrc", f) for f in os.listdir(os.path.
         os.path.join(REPO, "include", "agx_steplog.h"), os.path.join(REPO, "include", "agx_priority.h"),
         os.path.join(REPO, "include", "agx_augment.h"), os.path.join(REPO, "include", "agx_sequence.h"),
         os.path.join(REPO, "include", "agx_rollout.h"), os.path.join(REPO, "include", "agx_vtrace.h"),
-        os.path.join(REPO, "include", "agx_minibatch.h"), os.path.join(REPO, "include", "agx_retrace.h")]
+        os.path.join(REPO, "include", "agx_minibatch.h"), os.path.join(REPO, "include", "agx_retrace.h"),
+        os.path.join(REPO, "include", "agx_chunks.h")]
 # the measured dead ends (csrc/experiments/): compiled only into libagx_exp.so, for tools/ and tests/test_gpu_variants.py
 EXP_DEPS = sorted(os.path.join(HERE, "csrc", "experiments", f) for f in os.listdir(os.path.join(HERE, "csrc", "experiments")))
 OUT_DIR = os.path.join(HERE, "lib")

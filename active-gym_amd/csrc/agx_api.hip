@@ -1290,3 +1290,4 @@ int agx_step_flexible_packed(agx_ctx *ctx, const uint8_t *d_screens, int screens
 #include "agx_vtrace_impl.h"
 #include "agx_minibatch_impl.h"
 #include "agx_retrace_impl.h"
+#include "agx_chunks_host.h"

@@ -19,6 +19,7 @@
 //   k_slot_fold<VtraceFold>  K13 V-trace targets and policy-gradient advantages over a gathered rollout, for actor-learner training
 //   k_mb_count / k_mb_scan / k_mb_take / k_mb_scatter  K15  minibatches on a gathered rollout: its LIVE / BOOT slot lists, shuffled
 //   k_retrace_direct  K16  Retrace-family Q-returns folded backward along the sequences of a sequence-replay batch
+//   k_chunk_scan / k_chunk_take  K17  minibatches of chunks of consecutive steps on a gathered rollout, for recurrent learners
 //
 // The fixed fovea's phases are stated once in agx_fixed_phases.h (K2, K5, K6, K10, K11 run them).  The three kernels that re-create
 // observation planes from history rows - k_history_observe, k_history_observe_shifted, k_sequence_observe - are one body,
@@ -53,6 +54,7 @@
 #include "agx_k14_step_packed.h"
 #include "agx_k15_minibatch.h"
 #include "agx_k16_retrace.h"
+#include "agx_k17_chunks.h"
 #ifdef AGX_EXPERIMENTS
 #include "experiments/agx_experiments.h"   // measured dead ends: tools/ and the variants test only, never in libagx.so
 #include "experiments/agx_packed_wave.h"
